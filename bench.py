@@ -1,6 +1,12 @@
 """Benchmark: audio-frames/s through the ChunkFormer encoder (masked batch) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step and
+the roofline of the dominant kernel, whose launches are timed inside the K steps).  --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy.  --full adds every measurement that takes
+runs of its own: the CTC head and the collectives, end_to_end_ms, the per-class breakdown and the CPU
+baseline.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`
 (WORLD_SIZE must equal N, else the run exits non-zero), or started plainly, in which case bench.py
@@ -29,8 +35,8 @@ ranks step time.
 
 roofline: the dominant kernel is the FFN w_1 GEMM with its fused bias + SiLU epilogue
 (2 x 64N x 512 x 2048 FLOP per launch); its per-launch time is measured live with HIP events on
-the launch stream (libcfm in-stream profiler) over the timed steps.  end_to_end_ms: the same step
-plus the fused CTC ids head and, at N > 1, the ids all-gather (max over ranks).  cpu_baseline:
+the launch stream (libcfm in-stream profiler) over the timed steps.  With --full: end_to_end_ms, the
+same step plus the fused CTC ids head and, at N > 1, the ids all-gather (max over ranks); cpu_baseline,
 the CPU oracle (oracle/encoder_ref.py, torch fp32) on a bounded sample of the same workload, and
 on one 30 s utterance (configs[0]).
 """
@@ -240,6 +246,31 @@ def class_rooflines(prof, n_chunks: int, cfg, dtype: str, profiled: bool):
     return out
 
 
+DUMP_BYTES = 24 << 20   # per dumped array; a run dumps at most two large ones (64 MB in all)
+
+
+def dump_outputs(dirname: str, arrays, suffix: str = ""):
+    """--dump-outputs: write each named tensor as <dirname>/<name><suffix>.npy, floating point as float32 and
+    integers as float64.  A tensor over DUMP_BYTES is cut to a fixed sample of its rows (dim 0 after
+    flattening to [-1, last dim]; torch.Generator seed 0, ascending), the row numbers beside it in
+    <name>_rows<suffix>.npy, so that two builds dump the same rows."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t)
+        if t.dim() > 2:
+            t = t.reshape(-1, t.shape[-1])
+        row_bytes = 4 * (t.shape[-1] if t.dim() == 2 else 1)
+        keep = DUMP_BYTES // row_bytes
+        if t.dim() >= 1 and t.shape[0] > keep:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(0, rows.to(t.device))
+            np.save(os.path.join(dirname, f"{name}_rows{suffix}.npy"), rows.numpy().astype(np.float64))
+        a = t.detach().cpu()
+        a = a.to(torch.float32 if a.is_floating_point() else torch.float64).numpy()
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), a)
+
+
 def apply_opts(enc, opts):
     for kv in opts:
         k, v = kv.split("=")
@@ -281,9 +312,15 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--minutes", type=float, default=None,
                     help="audio minutes: per GPU for masked (240), of the whole batch for sharded (980)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64; outputs over 24 MB as a fixed seeded sample of their rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CTC head and collective timings, "
+                         "end_to_end_ms, the per-class breakdown and roofline, the CPU baseline")
     ap.add_argument("--no-gather-logp", action="store_true", help="sharded: skip the bf16 log-prob all-gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="--full without the per-class breakdown")
     ap.add_argument("--config", default="auto", choices=["auto", "masked", "sharded", "endless", "full", "fbank"],
                     help="auto = masked at 1 GPU, sharded at N > 1; masked = configs[1] (240 min per GPU, the "
                          "headline line); sharded = configs[2] (one 980-min batch over all ranks); endless = "
@@ -314,6 +351,8 @@ def main():
                     help="attention heads of the d=512 model: 8 (chunkformer-large, BASELINE) or 4 (head_dim 128, "
                          "the reference's shipped d=512 recipes)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     env_world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if env_world == 0 and args.gpus > 1:
         if args.config in ("endless", "full", "fbank"):
@@ -418,19 +457,27 @@ def main():
     busy, busy_clk, busy_src = committed_mfma_busy(roof_cls) if profiled else (None, None, None)
     step_flops = n_chunks * flops_per_chunk(cfg) + cfg.num_blocks * 2 * (L + 2 * C + R - 1) * cfg.d_model ** 2
 
-    # ---- CTC head + the collectives (timed separately; not part of `value`)
-    enc_out = out[0]
-    enc.ctc_log_softmax(enc_out, want_logp=False)   # first call loads the kernel
-    torch.cuda.synchronize()
-    tc = time.perf_counter()
-    _, ids = enc.ctc_log_softmax(enc_out, want_logp=False)   # fused argmax head (ids only)
-    torch.cuda.synchronize()
-    ctc_ms = (time.perf_counter() - tc) * 1e3
-    gather_ms = gather_lp_ms = None
     # the kept rows of every piece, in shard order (the layout gather_* expects)
+    enc_out = out[0]
     starts = torch.tensor([0] + list(out[2][:-1])).cumsum(0) * C
     idx = torch.cat([torch.arange(int(s) + p.skip, int(s) + p.skip + p.rows) for s, p in zip(starts, mine)]).to(dev)
-    if world > 1:
+    if args.dump_outputs:
+        # what the caller of the last timed step received: the encoder rows this rank answers for (the
+        # rows past an utterance's length in its last chunk are padding), the output lengths, the chunk counts
+        dump_outputs(args.dump_outputs, {"encoder_out": enc_out.reshape(-1, cfg.d_model).index_select(0, idx),
+                                         "xs_lens": out[1], "n_chunks": torch.tensor(out[2])},
+                     suffix="" if rank == 0 else f"_rank{rank}")
+
+    # ---- CTC head + the collectives (timed separately; not part of `value`)
+    ctc_ms = gather_ms = gather_lp_ms = None
+    if args.full:
+        enc.ctc_log_softmax(enc_out, want_logp=False)   # first call loads the kernel
+        torch.cuda.synchronize()
+        tc = time.perf_counter()
+        _, ids = enc.ctc_log_softmax(enc_out, want_logp=False)   # fused argmax head (ids only)
+        torch.cuda.synchronize()
+        ctc_ms = (time.perf_counter() - tc) * 1e3
+    if args.full and world > 1:
         flat = ids.reshape(-1).index_select(0, idx)
         dist.barrier()
         torch.cuda.synchronize()
@@ -448,54 +495,56 @@ def main():
             torch.cuda.synchronize()
             gather_lp_ms = (time.perf_counter() - tg) * 1e3
             del logp
-    del out, enc_out, ids
-    # the gather's per-utterance reassembly at configs[2]'s world 8, timed on this GPU alone: one
-    # index_select of the gathered [8, max_rows] ids with the plan's cached index, then views
-    assemble_ms = None
-    if sharded and rank == 0:
-        sh8 = plan_shards(lens_all, 8, C, L, R, cfg.num_blocks)
-        buf8 = torch.zeros(8, max(1, max(sum(p.rows for p in s_) for s_ in sh8)), dtype=torch.int32, device=dev)
-        _assemble(buf8, sh8, len(lens_all), lens_all)   # builds and uploads the plan's index once
-        torch.cuda.synchronize()
-        ta = time.perf_counter()
-        for _ in range(5):
-            _assemble(buf8, sh8, len(lens_all), lens_all)
-        torch.cuda.synchronize()
-        assemble_ms = (time.perf_counter() - ta) / 5 * 1e3
-        del buf8
-
-    # ---- end to end: the step + the fused CTC ids head + (N > 1) the ids all-gather with the
-    # per-utterance reassembly on every rank; K steps between barriers, max over ranks
-    def e2e():
-        o = step()
-        _, ids_ = enc.ctc_log_softmax(o[0], want_logp=False)
-        if world > 1:
-            gather_ids(ids_.reshape(-1).index_select(0, idx), shards, lens_all)
-        return ids_
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        e2e()
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    te = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(te, op=dist.ReduceOp.MAX)
-    e2e_ms = float(te.item()) / args.steps * 1e3
-
+    del out, enc_out
+    assemble_ms = e2e_ms = None
     breakdown = by_class = None
-    if not args.no_breakdown:
-        enc.set_option("profile_reset", 1)
-        enc.set_option("profile", (1 << len(_lib.PROFILE_CLASSES)) - 1)
-        step()
+    if args.full:
+        del ids
+        # the gather's per-utterance reassembly at configs[2]'s world 8, timed on this GPU alone: one
+        # index_select of the gathered [8, max_rows] ids with the plan's cached index, then views
+        if sharded and rank == 0:
+            sh8 = plan_shards(lens_all, 8, C, L, R, cfg.num_blocks)
+            buf8 = torch.zeros(8, max(1, max(sum(p.rows for p in s_) for s_ in sh8)), dtype=torch.int32, device=dev)
+            _assemble(buf8, sh8, len(lens_all), lens_all)   # builds and uploads the plan's index once
+            torch.cuda.synchronize()
+            ta = time.perf_counter()
+            for _ in range(5):
+                _assemble(buf8, sh8, len(lens_all), lens_all)
+            torch.cuda.synchronize()
+            assemble_ms = (time.perf_counter() - ta) / 5 * 1e3
+            del buf8
+
+        # ---- end to end: the step + the fused CTC ids head + (N > 1) the ids all-gather with the
+        # per-utterance reassembly on every rank; K steps between barriers, max over ranks
+        def e2e():
+            o = step()
+            _, ids_ = enc.ctc_log_softmax(o[0], want_logp=False)
+            if world > 1:
+                gather_ids(ids_.reshape(-1).index_select(0, idx), shards, lens_all)
+            return ids_
+        if world > 1:
+            dist.barrier()
         torch.cuda.synchronize()
-        enc.set_option("profile", 0)
-        prof_all = _lib.profile_read(enc._h)
-        breakdown = {k: round(v[0], 3) for k, v in prof_all.items() if v[1]}
-        by_class = class_rooflines(prof_all, n_chunks, cfg, args.dtype, profiled)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            e2e()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        te = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(te, op=dist.ReduceOp.MAX)
+        e2e_ms = float(te.item()) / args.steps * 1e3
+
+        if not args.no_breakdown:
+            enc.set_option("profile_reset", 1)
+            enc.set_option("profile", (1 << len(_lib.PROFILE_CLASSES)) - 1)
+            step()
+            torch.cuda.synchronize()
+            enc.set_option("profile", 0)
+            prof_all = _lib.profile_read(enc._h)
+            breakdown = {k: round(v[0], 3) for k, v in prof_all.items() if v[1]}
+            by_class = class_rooflines(prof_all, n_chunks, cfg, args.dtype, profiled)
 
     if rank == 0:
         res = {
@@ -547,10 +596,12 @@ def main():
                          "clock_ghz_pmc": busy_clk if profiled else None,
                          "mfma_busy_source": busy_src if profiled else None},
             "step_tflops_algorithmic": round(step_flops / (dt_max / args.steps) / 1e12, 1),
-            "ctc_ms": round(ctc_ms, 3),
+            # from here on: measured by runs of their own, null without --full
+            "full": bool(args.full),
+            "ctc_ms": round(ctc_ms, 3) if ctc_ms is not None else None,
             "allgather_ids_ms": round(gather_ms, 3) if gather_ms is not None else None,
-            "end_to_end_ms": round(e2e_ms, 3),
-            "end_to_end_value": round(total_frames / (e2e_ms / 1e3), 1),
+            "end_to_end_ms": round(e2e_ms, 3) if e2e_ms is not None else None,
+            "end_to_end_value": round(total_frames / (e2e_ms / 1e3), 1) if e2e_ms is not None else None,
             "end_to_end_note": ("encoder step + fused CTC ids head" +
                                 (" + ids all_gather_into_tensor and per-utterance reassembly" if world > 1 else "")),
             "allgather_logp_bf16_ms": round(gather_lp_ms, 3) if gather_lp_ms is not None else None,
@@ -558,7 +609,7 @@ def main():
             "breakdown_ms": breakdown,
             "roofline_by_class": by_class,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(lens_all)
         print(json.dumps(res), flush=True)
     if world > 1:
@@ -638,25 +689,32 @@ def bench_single(args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     value = frames * args.steps / dt
-    # roofline kernel: per-launch time from in-stream HIP events on an eager call of the same shape
-    enc.set_option("profile_reset", 1)
-    enc.set_option("profile", 1 << _lib.PROFILE_CLASSES.index(roof_cls))
-    prof_call()
-    torch.cuda.synchronize()
-    enc.set_option("profile", 0)
-    ms1, n1 = _lib.profile_read(enc._h)[roof_cls]
-    avg_s = ms1 / max(n1, 1) / 1e3
-    # per-class breakdown of one eager call (endless: one full segment)
-    enc.set_option("profile_reset", 1)
-    enc.set_option("profile", (1 << len(_lib.PROFILE_CLASSES)) - 1)
-    prof_call()
-    torch.cuda.synchronize()
-    enc.set_option("profile", 0)
-    breakdown = {k: round(v[0], 3) for k, v in _lib.profile_read(enc._h).items() if v[1]}
+    if args.dump_outputs:
+        # endless: the CTC ids [1, T', 1] of the whole utterance; full: the encoder rows and their lengths
+        dump_outputs(args.dump_outputs, {"ctc_ids": last} if args.config == "endless" else
+                     {"encoder_out": last[0], "encoder_lens": last[1]})
+    del last
+    ms1 = n1 = avg_s = breakdown = None
+    if args.full:
+        # roofline kernel: per-launch time from in-stream HIP events on an eager call of the same shape
+        enc.set_option("profile_reset", 1)
+        enc.set_option("profile", 1 << _lib.PROFILE_CLASSES.index(roof_cls))
+        prof_call()
+        torch.cuda.synchronize()
+        enc.set_option("profile", 0)
+        ms1, n1 = _lib.profile_read(enc._h)[roof_cls]
+        avg_s = ms1 / max(n1, 1) / 1e3
+        # per-class breakdown of one eager call (endless: one full segment)
+        enc.set_option("profile_reset", 1)
+        enc.set_option("profile", (1 << len(_lib.PROFILE_CLASSES)) - 1)
+        prof_call()
+        torch.cuda.synchronize()
+        enc.set_option("profile", 0)
+        breakdown = {k: round(v[0], 3) for k, v in _lib.profile_read(enc._h).items() if v[1]}
     peak = PEAK_TFLOPS[args.dtype]
     if roof_cls == "ffn_w1_gemm":
         fl_launch = 2.0 * rows * ff_ * d_
@@ -674,8 +732,10 @@ def bench_single(args):
                    "parallelism": "single GPU"},
         "roofline": {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 1) if achieved else None,
                      "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4) if achieved else None,
-                     "traffic": None, "flops_per_launch": fl_launch, "avg_launch_ms": round(avg_s * 1e3, 4),
-                     "launches": n1},
+                     "traffic": None, "flops_per_launch": fl_launch,
+                     "avg_launch_ms": round(avg_s * 1e3, 4) if n1 else None, "launches": n1},
+        # the roofline's launch time and the breakdown come from eager calls of their own: null without --full
+        "full": bool(args.full),
         "breakdown_ms_one_call": breakdown,
     }
     print(json.dumps(res), flush=True)
@@ -684,8 +744,8 @@ def bench_single(args):
 def bench_fbank(args):
     """GPU Kaldi fbank (§8(f) row 2, chunkformer_model.py:306-314 parameters) over `--hours` of
     16 kHz int16-scale synthetic audio resident in HBM: frames/s, HBM roofline of the kernel
-    (samples in + features out per launch), the CPU oracle (oracle/fbank_ref.py, torch float32,
-    all cores) on 60 s of the same audio beside it."""
+    (samples in + features out per launch); with --full the CPU oracle (oracle/fbank_ref.py, torch
+    float32, all cores) on 60 s of the same audio beside it."""
     from chunkformer_amd.fbank import KaldiFbank
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
@@ -703,22 +763,30 @@ def bench_fbank(args):
     t0 = time.perf_counter()
     e0.record(st)
     for _ in range(args.steps):
-        fb(x)
+        feats = fb(x)
     e1.record(st)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     kern_s = e0.elapsed_time(e1) / 1e3 / args.steps
     nbytes = n * 4 + frames * 80 * 4
-    from oracle import fbank_ref
-    xs = x[: 60 * 16000].cpu()
-    cpu_model, threads = host_cpu()
-    torch.set_num_threads(threads)
-    c0 = time.perf_counter()
-    reps = 0
-    while time.perf_counter() - c0 < 10.0:
-        fbank_ref.fbank(xs, num_mel_bins=80, frame_length=25, frame_shift=10, dither=0.0, energy_floor=0.0)
-        reps += 1
-    cpu_fps = reps * fbank_ref.num_frames(xs.numel(), 400, 160) / (time.perf_counter() - c0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"fbank": feats})
+    del feats
+    cpu = None
+    if args.full:
+        from oracle import fbank_ref
+        xs = x[: 60 * 16000].cpu()
+        cpu_model, threads = host_cpu()
+        torch.set_num_threads(threads)
+        c0 = time.perf_counter()
+        reps = 0
+        while time.perf_counter() - c0 < 10.0:
+            fbank_ref.fbank(xs, num_mel_bins=80, frame_length=25, frame_shift=10, dither=0.0, energy_floor=0.0)
+            reps += 1
+        cpu_fps = reps * fbank_ref.num_frames(xs.numel(), 400, 160) / (time.perf_counter() - c0)
+        cpu = {"value": round(cpu_fps, 1), "unit": "fbank-frames/s", "cores": threads, "cpu": cpu_model,
+               "kind": "port", "sample": "oracle/fbank_ref.py (torchaudio kaldi.fbank restated, torch "
+                                         "float32 CPU) on the first 60 s of the same audio, repeated ~10 s"}
     res = {
         "metric": "fbank frames/sec (80-dim Kaldi log-mel, 25/10 ms, povey) from 16 kHz audio resident in HBM",
         "value": round(frames * args.steps / dt, 1), "unit": "fbank-frames/s", "n_gpus": 1, "steps": args.steps,
@@ -737,10 +805,10 @@ def bench_fbank(args):
                               "achieved_tflops": round(FBANK_FLOPS_PER_FRAME * frames / kern_s / 1e12, 2),
                               "peak_fp32_vector_tflops": 157.3,
                               "frac": round(FBANK_FLOPS_PER_FRAME * frames / kern_s / 1e12 / 157.3, 4)}},
-        "cpu_baseline": {"value": round(cpu_fps, 1), "unit": "fbank-frames/s", "cores": threads, "cpu": cpu_model,
-                         "kind": "port", "sample": "oracle/fbank_ref.py (torchaudio kaldi.fbank restated, torch "
-                                                   "float32 CPU) on the first 60 s of the same audio, repeated ~10 s"},
+        "full": bool(args.full),
     }
+    if cpu is not None:
+        res["cpu_baseline"] = cpu
     print(json.dumps(res), flush=True)
 
 
