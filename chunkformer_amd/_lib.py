@@ -109,7 +109,10 @@ cfm_rnnt_error = _sig("cfm_rnnt_error", I32, P, P, I32)
 # include/cfm_ops.h
 cfm_op_gemm = _sig("cfm_op_gemm", I32, I32, I32, I32, P, I32, P, I32, I32, I32, I32, P, ctypes.c_float, P, I32, I32, P,
                    I32, P, I32, P, I32, P)
-EXPORTED_OPS = ["cfm_op_gemm"]
+ATTN_GENERIC, ATTN_RING, ATTN_A128, ATTN_DENSE = 0, 1, 2, 3
+cfm_op_attention = _sig("cfm_op_attention", I32, I32, I32, P, P, I32, P, I32, I32, P, P, P, I32, I32, I32, I32, I32, P,
+                        I32, P, I32, I32, I32, I32, P)
+EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention"]
 
 EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_destroy", "cfm_model_set_option",
             "cfm_plan_masked", "cfm_plan_masked_ex", "cfm_plan_padded", "cfm_workspace_bytes_masked", "cfm_workspace_bytes_padded",

@@ -32,7 +32,7 @@ def _sources():
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs.append(os.path.join(os.path.dirname(HERE), "include", "cfm.h"))
+    hs += [os.path.join(os.path.dirname(HERE), "include", h) for h in ("cfm.h", "cfm_ops.h")]
     return hs
 
 

@@ -265,7 +265,9 @@ CFM_DEV int sw128(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7))
                      // with the conflict-free skew: off 4.22 vs on 4.30 ms/step, one-process A/B)
 #endif
 #ifndef RING_V4
-#define RING_V4 1   // next-pair staging in row quads (8-B V^T stores, half the store instructions; C % 4 == 0)
+#define RING_V4 1   // next-pair staging in row quads (8-B V^T stores, half the store instructions) when W % 4 == 0:
+                    // the staged rows start at flat row c0 C + (cp - c0) C + W + C + 4k = W (mod 4), and a quad must
+                    // not straddle the ring wrap (RING % 4 == 0) nor split an 8-B V^T store; W % 4 == 2 stages in pairs
 #endif
 #ifndef ATTN_PRIO
 #define ATTN_PRIO 1   // static wave priority: 1 = the second-dispatched half (waves 4-7) at s_setprio 1 (ring attention
@@ -417,8 +419,9 @@ CFM_DEV void skew_finish(const SkewRd& r, E (&bd)[2][4]) {
 
 // DG: the timing / A-B hooks of `diag` are compiled in (the production instantiation has none of their
 // uniform branches inside the tile loop, which would cut it into basic blocks the scheduler cannot
-// interleave across); NTI = W / 64 when W is whole 64-key tiles (1..5), else 0
-template <bool DG, int NTI, typename E = bf16>
+// interleave across); NTI = W / 64 when W is whole 64-key tiles (1..5), else 0; V4 = next-pair staging in row
+// quads (the launcher: RING_V4 && W % 4 == 0), else in row pairs
+template <bool DG, int NTI, typename E = bf16, bool V4 = (RING_V4 != 0)>
 __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
     const E* __restrict__ Q, const E* __restrict__ KV, int kv_rows, const E* __restrict__ P, int p_rows,
     const float* __restrict__ pos_u, const float* __restrict__ pos_v, const int32_t* __restrict__ desc, int n_chunks,
@@ -466,7 +469,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
 #pragma unroll
     for (int e = 0; e < 8; ++e) *reinterpret_cast<ex2_*>(vt + (ch * 8 + e) * VT_PITCH_B + rr * 2) = (ex2_){a[e], b[e]};
   };
-  // RING_V4: four consecutive rows (frow % 4 == 0) x one 16-B chunk: each V^T dim row gets one 8-B store
+  // V4: four consecutive rows (frow % 4 == 0) x one 16-B chunk: each V^T dim row gets one 8-B store
   auto stage_quad = [&](int frow, int ch, const u32x4 (&k)[4], const u32x4 (&v)[4]) {
     const int rr = frow % RING;   // multiple of 4; rr + 3 < RING
 #pragma unroll
@@ -570,7 +573,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
     const int pf_pairs = n_new / 2;
     u32x4 pk0[2], pv0[2], pk1[2], pv1[2];
     int pf_row[2], pf_ch[2];
-    if constexpr (RING_V4) {
+    if constexpr (V4) {
       // quads: 2C / 4 <= 32 row quads x 8 chunks <= 256 items, one per thread of the first half
       const int pf_quads = n_new / 4;
       pf_row[0] = pf_row[1] = -1;
@@ -839,7 +842,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
     }
     // ---- the prefetched rows replace the first 2C rows of this pair's windows (no longer needed)
     if ((diag & 15) != 7) __syncthreads();
-    if constexpr (RING_V4) {
+    if constexpr (V4) {
       if (pf_row[0] >= 0) {
         const u32x4 kq[4] = {pk0[0], pk1[0], pk0[1], pk1[1]}, vq[4] = {pv0[0], pv1[0], pv0[1], pv1[1]};
         stage_quad(pf_row[0], pf_ch[0], kq, vq);
@@ -874,10 +877,17 @@ int chunk_attention_masked_ring(const E* q, const E* kv, int kv_rows, const E* P
   const int nch = (n_chunks + gx - 1) / gx;
   const dim3 grid(gx, H);
 #define RING_L(DG_, NT_)                                                                                             \
-  hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, NT_, E>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, pos_u, \
+  hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, NT_, E, RING_V4 != 0>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, pos_u, \
                      pos_v, desc, n_chunks, H, C, W, out, diag, nch, p_ld)
+#define RING_P(DG_)                                                                                                   \
+  hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, 0, E, false>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, \
+                     pos_u, pos_v, desc, n_chunks, H, C, W, out, diag, nch, p_ld)
   const int nti = W % 64 == 0 ? W / 64 : 0;
-  if (diag) {
+  if (W % 4) {   // W % 4 == 2 (never whole 64-key tiles): pair staging
+    if (diag) RING_P(true);
+    else RING_P(false);
+  }
+  else if (diag) {
     if (nti == 5) RING_L(true, 5);
     else RING_L(true, 0);
   }
@@ -888,6 +898,7 @@ int chunk_attention_masked_ring(const E* q, const E* kv, int kv_rows, const E* P
   else if (nti == 1) RING_L(false, 1);
   else RING_L(false, 0);
 #undef RING_L
+#undef RING_P
   CFM_CHECK_LAUNCH();
   return 0;
 }

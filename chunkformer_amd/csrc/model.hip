@@ -980,6 +980,56 @@ cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, i
   return CFM_OK;
 }
 
+cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const void* kv, int32_t kv_rows, const void* P,
+                            int32_t p_rows, int32_t p_ld, const float* pos_u, const float* pos_v, const int32_t* desc,
+                            int32_t n_desc, int32_t H, int32_t dk, int32_t C, int32_t W, void* out, int32_t min_chunks,
+                            void* vt, int32_t vt_ld, int32_t nutt, int32_t nd, int32_t t_keys, cfm_stream stream) {
+  static const char* const KNAME[] = {"generic", "ring", "a128", "dense"};
+  if (!q || !kv || !P || !pos_u || !pos_v || !desc || !out) return set_error(CFM_ERR_VALUE, "attention: null argument");
+  if (kernel < CFM_ATTN_GENERIC || kernel > CFM_ATTN_DENSE) return set_error(CFM_ERR_VALUE, "attention: unknown kernel");
+  if (dtype != CFM_DTYPE_F32 && dtype != CFM_DTYPE_BF16 && dtype != CFM_DTYPE_F16)
+    return set_error(CFM_ERR_VALUE, "attention: unknown dtype");
+  if (H <= 0 || kv_rows <= 0 || p_rows <= 0 || n_desc <= 0 || (dk != 64 && dk != 128) || (p_ld > 0 && p_ld < H * dk))
+    return set_error(CFM_ERR_VALUE, "attention: bad H / dk / kv_rows / p_rows / p_ld / n_desc");
+  hipStream_t st = (hipStream_t)stream;
+  int r = -1;   // -1: the selected launcher does not take this configuration (never another kernel instead)
+  if (kernel == CFM_ATTN_GENERIC) {
+    if (dtype == CFM_DTYPE_F32)
+      r = chunk_attention<float>((const float*)q, (const float*)kv, kv_rows, (const float*)P, p_rows, pos_u, pos_v, desc,
+                                 n_desc, H, dk, (float*)out, st, p_ld);
+    else if (dtype == CFM_DTYPE_F16)
+      r = chunk_attention<f16>((const f16*)q, (const f16*)kv, kv_rows, (const f16*)P, p_rows, pos_u, pos_v, desc, n_desc,
+                               H, dk, (f16*)out, st, p_ld);
+    else
+      r = chunk_attention<bf16>((const bf16*)q, (const bf16*)kv, kv_rows, (const bf16*)P, p_rows, pos_u, pos_v, desc,
+                                n_desc, H, dk, (bf16*)out, st, p_ld);
+  } else if (kernel == CFM_ATTN_RING) {
+    if (dk == 64 && dtype == CFM_DTYPE_BF16)
+      r = chunk_attention_masked_bf16((const bf16*)q, (const bf16*)kv, kv_rows, (const bf16*)P, p_rows, pos_u, pos_v, desc,
+                                      n_desc, H, C, W, (bf16*)out, st, 0, p_ld, 1, min_chunks);
+    else if (dk == 64 && dtype == CFM_DTYPE_F16)
+      r = chunk_attention_masked_f16((const f16*)q, (const f16*)kv, kv_rows, (const f16*)P, p_rows, pos_u, pos_v, desc,
+                                     n_desc, H, C, W, (f16*)out, st, 0, p_ld, 1, min_chunks);
+  } else if (kernel == CFM_ATTN_A128) {
+    if (dtype == CFM_DTYPE_BF16 && attention_a128_eligible(C, W, p_rows, dk)) {
+      if (!vt || vt_ld < kv_rows || vt_ld % 8) return set_error(CFM_ERR_VALUE, "attention: a128 needs vt [H * 128][vt_ld], vt_ld >= kv_rows, vt_ld % 8 == 0");
+      KCHK(vt_transpose_bf16((const bf16*)kv, kv_rows, H, (bf16*)vt, vt_ld, st));
+      r = chunk_attention_masked_a128((const bf16*)q, (const bf16*)kv, kv_rows, (const bf16*)vt, vt_ld, (const bf16*)P,
+                                      p_rows, p_ld > 0 ? p_ld : H * dk, pos_u, pos_v, desc, n_desc, H, C, W, (bf16*)out, st);
+    }
+  } else {
+    if (nutt <= 0 || nd <= 0 || (int64_t)nutt * nd != n_desc)
+      return set_error(CFM_ERR_VALUE, "attention: dense needs n_desc == nutt * nd");
+    if (dtype == CFM_DTYPE_BF16)
+      r = full_attention_bf16((const bf16*)q, (const bf16*)kv, kv_rows, (const bf16*)P, p_rows, pos_u, pos_v, desc, nutt,
+                              nd, H, dk, t_keys, (bf16*)out, st, p_ld);
+  }
+  if (r == -1)
+    return set_error(CFM_ERR_ASSERT, std::string("attention: the ") + KNAME[kernel] + " kernel does not take this configuration");
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string("attention (") + KNAME[kernel] + "): " + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
 size_t cfm_ctc_workspace_bytes(const cfm_model* m, int32_t rows) { return m ? m->ctc_ws_bytes(rows) : 0; }
 
 cfm_status cfm_ctc_logprobs(const cfm_model* m, const float* enc, int32_t rows, float* logp, int32_t* ids, void* ws,

@@ -33,6 +33,29 @@ cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, i
                        int32_t row_off, void* out2, int32_t d, float* x, int32_t ldx, const uint8_t* rowmask,
                        int32_t variant, cfm_stream stream);
 
+/* One attention kernel on caller-owned buffers (csrc/attention.hip, attention128.hip).  `kernel` names the
+ * kernel and nothing else runs in its place: when the selected kernel does not take the configuration
+ * (dtype, dk, C, W, p_rows, T') the call launches nothing, leaves `out` untouched and returns CFM_ERR_ASSERT
+ * with a message naming the kernel; a HIP failure is CFM_ERR_RUNTIME.
+ *   q [rows][H*dk], out [rows][H*dk], kv [kv_rows][H][K dk | V dk] (dtype elements); P [p_rows] rows of stride
+ *   p_ld (0 = H*dk), head h at column h*dk; pos_u / pos_v [H*dk] f32; desc [n_desc][8] int32 on the device:
+ *   (Q_ROW0, NQ, KV_ROW0, KEY_LO, KEY_HI, P_BASE, Q_VALID, 0).  For descriptor b, head h, i < NQ, j in [KEY_LO, KEY_HI):
+ *     s(i,j) = ((q_i + u).K[KV_ROW0 + j] + (q_i + v).P[P_BASE - i + j]) / sqrt(dk),  out_i = softmax_j(s) . V;
+ *   rows i >= Q_VALID and rows without keys are written as 0.
+ * GENERIC: any descriptors, f32 / bf16 / f16, dk 64 or 128.
+ * RING:    bf16 / f16, dk 64; the descriptors of a masked-batch plan with one block per chunk (chunk c: Q_ROW0 =
+ *          KV_ROW0 = c*C, NQ = Q_VALID = C, P_BASE = C-1), W = L + C + R; min_chunks = shortest run of chunks per
+ *          block (the model's "attn_min_chunks"; >= 2).
+ * A128:    bf16, dk 128, the same descriptors at C = 64; vt = V^T scratch [H*128][vt_ld] (vt_ld >= kv_rows,
+ *          a multiple of 8), filled here by the transpose kernel before the attention kernel, as the model does.
+ * DENSE:   bf16, dk 64; a full-attention padded plan: nutt utterances x nd consecutive 64-query descriptors
+ *          (n_desc = nutt * nd), t_keys = T' <= 384. */
+typedef enum { CFM_ATTN_GENERIC = 0, CFM_ATTN_RING = 1, CFM_ATTN_A128 = 2, CFM_ATTN_DENSE = 3 } cfm_attn_kernel;
+cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const void* kv, int32_t kv_rows, const void* P,
+                            int32_t p_rows, int32_t p_ld, const float* pos_u, const float* pos_v, const int32_t* desc,
+                            int32_t n_desc, int32_t H, int32_t dk, int32_t C, int32_t W, void* out, int32_t min_chunks,
+                            void* vt, int32_t vt_ld, int32_t nutt, int32_t nd, int32_t t_keys, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

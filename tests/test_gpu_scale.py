@@ -490,10 +490,11 @@ def test_head_dim_128_kernel_vs_generic(model_4h, C, L, R):
 
 
 @pytest.mark.parametrize("C,L,R", [(64, 128, 128), (64, 64, 64), (64, 0, 0), (32, 64, 32), (48, 16, 32),
-                                   (16, 32, 32), (64, 128, 0)])
+                                   (16, 32, 32), (64, 128, 0), (64, 62, 0), (32, 30, 0)])
 def test_ring_kernel_shapes_vs_generic(large, C, L, R):
     """The dk = 64 ring kernel against the generic kernel on chunkformer-large (12 layers, 8 heads)
-    over the chunk / context shapes it accepts (C % 16 == 0, W <= 320), utterance edges included."""
+    over the chunk / context shapes it accepts (C % 16 == 0, W even and <= 320; the last two have
+    W % 4 == 2: next-pair staging in row pairs), utterance edges included."""
     _, _, models = large
     rel = _fast_vs_generic(models["bf16"], [20_000, 519, 3000, 7, 1100, 9000], 19, C, L, R)
     print(f"ring kernel vs generic (C={C} L={L} R={R}): rel-L2 {rel:.2e}")
