@@ -106,6 +106,21 @@ CFM_RNNT_ONE_WORKGROUP = 1
 cfm_rnnt_set_option = _sig("cfm_rnnt_set_option", I32, P, ctypes.c_char_p, I64)
 cfm_rnnt_grid_blocks = _sig("cfm_rnnt_grid_blocks", I32, P, I32)
 cfm_rnnt_error = _sig("cfm_rnnt_error", I32, P, P, I32)
+# classification consumer (include/cfm.h)
+CLS_MAX_TASKS = 16
+
+
+class CfmClsConfig(ctypes.Structure):
+    _fields_ = [("enc_dim", I32), ("n_tasks", I32), ("num_classes", I32 * CLS_MAX_TASKS)]
+
+
+cfm_cls_create = _sig("cfm_cls_create", I32, ctypes.POINTER(CfmClsConfig), ctypes.POINTER(CfmTensorView), I32, I32,
+                      ctypes.POINTER(P))
+cfm_cls_destroy = _sig("cfm_cls_destroy", None, P)
+cfm_cls_pool_workspace_bytes = _sig("cfm_cls_pool_workspace_bytes", SZ, I32, I32, I32)
+cfm_cls_workspace_bytes = _sig("cfm_cls_workspace_bytes", SZ, P, I32, I32)
+cfm_cls_pool = _sig("cfm_cls_pool", I32, P, I32, I32, P, P, I32, P, P, SZ, P)
+cfm_cls_classify = _sig("cfm_cls_classify", I32, P, P, I32, P, P, I32, P, P, P, P, P, SZ, P)
 # include/cfm_ops.h
 cfm_op_gemm = _sig("cfm_op_gemm", I32, I32, I32, I32, P, I32, P, I32, I32, I32, I32, P, ctypes.c_float, P, I32, I32, P,
                    I32, P, I32, P, I32, P)
@@ -121,7 +136,9 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_plan_stream", "cfm_workspace_bytes_stream", "cfm_encode_stream",
             "cfm_fbank_create", "cfm_fbank_destroy", "cfm_fbank_num_frames", "cfm_fbank_compute",
             "cfm_rnnt_create", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
-            "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error"]
+            "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error",
+            "cfm_cls_create", "cfm_cls_destroy", "cfm_cls_pool_workspace_bytes", "cfm_cls_workspace_bytes",
+            "cfm_cls_pool", "cfm_cls_classify"]
 
 
 def profile_read(h):

@@ -21,10 +21,20 @@ the id -> text mapping (class2str) and the hh:mm:ss:ms formatting stay on the ho
 search on the device (transducer.py, cfm_rnnt_greedy) exactly where the reference calls
 optimized_search / batch_greedy_search (chunkformer_model.py:439-448, 533-543); their per-frame
 decisions [T, n_steps] go through get_output_with_timestamps' transducer branch (no collapse).
-`model: classification` checkpoints are out of scope and refused.
+`model: classification` checkpoints (config.yaml `model_conf.tasks`, init_model.py:106-116, with an
+optional label_mapping.json) run the reference's classification path on the device (classifier.py,
+cfm_cls_classify): masked mean pool of the encoder output over time + one linear head per task,
+
+  classify         classification_model.py:232-281   padded batch -> {task}_prediction / _probability
+  classify_audio   chunkformer_model.py:555-640      one input -> {task: {label, label_id, prob}}
+  batch_classify   (bin/classify.py's use case)      duration-budget grouping -> masked batch -> heads
+
+They have no CTC head; the ASR decoding methods raise ValueError on them and classify* raises
+ValueError on the other model types.
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import math
 import os
@@ -36,6 +46,7 @@ import torch
 from .config import EncoderConfig
 from .encoder import ChunkFormerEncoder
 from .streaming import EndlessGraphPipeline, EndlessGraphRunner, EndlessPipeline
+from .classifier import ClassifierConfig, ClassifierHeads
 from .transducer import RNNTConfig, RNNTGreedy
 
 Features = Union[torch.Tensor, np.ndarray, str]
@@ -182,14 +193,25 @@ def _load_features(x: Features, featurize=None) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- model
 class ChunkFormerModel:
-    """encoder + CTC head; the inference API of chunkformer_model.py on libcfm."""
+    """encoder + CTC head, RNN-T search or classification heads; the inference API of
+    chunkformer_model.py on libcfm."""
 
     def __init__(self, cfg: EncoderConfig, state_dict: Dict[str, torch.Tensor], dtype: str = "bf16", device=None,
                  char_dict: Optional[Dict[int, str]] = None, fbank_conf: Optional[dict] = None,
                  resample_conf: Optional[dict] = None, model_type: str = "asr_model",
-                 rnnt_config: Optional[RNNTConfig] = None):
-        if model_type not in ("asr_model", "transducer"):
-            raise AssertionError(f"model: {model_type} is out of scope (asr_model / transducer decoders only)")
+                 rnnt_config: Optional[RNNTConfig] = None, tasks: Optional[Dict[str, int]] = None,
+                 classifier_config: Optional[ClassifierConfig] = None,
+                 label_mapping: Optional[Dict[str, Dict[str, str]]] = None):
+        if model_type not in ("asr_model", "transducer", "classification"):
+            raise AssertionError(f"model: {model_type} is not one of asr_model / transducer / classification")
+        self.is_classification = model_type == "classification"
+        if self.is_classification:
+            if classifier_config is None:
+                if not tasks:
+                    raise ValueError("Classification model requires 'tasks' in model_conf")
+                classifier_config = ClassifierConfig(tasks=dict(tasks), enc_dim=cfg.d_model)
+            if cfg.vocab != 0:   # init_model.py:77: a classification model has no CTC head
+                cfg = dataclasses.replace(cfg, vocab=0)
         self.config = cfg
         self.model_type = model_type
         self.encoder = ChunkFormerEncoder(cfg, state_dict, device=device, dtype=dtype)
@@ -198,6 +220,10 @@ class ChunkFormerModel:
         if model_type == "transducer":
             rc = rnnt_config or RNNTConfig(vocab=cfg.vocab, enc_dim=cfg.d_model)
             self.rnnt = RNNTGreedy(rc, state_dict, self.device)
+        self.classifier = None
+        if self.is_classification:
+            self.classifier = ClassifierHeads(classifier_config, state_dict, self.device)
+        self.label_mapping = label_mapping
         self.char_dict = char_dict
         self.fbank_conf = dict(fbank_conf or {})
         self.resample_conf = dict(resample_conf or {})
@@ -238,7 +264,10 @@ class ChunkFormerModel:
           like load_checkpoint(strict=False) (checkpoint.py:26-41): keys present in the
           checkpoint win, so its `encoder.global_cmvn.{mean,istd}` buffers override the stats file
           exactly as load_state_dict does in the reference; model.safetensors is also accepted;
-        * vocab.txt ("token id" per line, file_utils.py:62-69) -> char_dict for text output.
+        * vocab.txt ("token id" per line, file_utils.py:62-69) -> char_dict for text output;
+        * `model: classification`: the heads come from model_conf.tasks (in their order), and
+          label_mapping.json ({task: {"id": label}}, chunkformer_model.py:200-205), when present,
+          names the predicted ids in classify_audio / batch_classify.
         There is no hub access: `path` must be a local directory."""
         import yaml
         if not os.path.isdir(path):
@@ -276,9 +305,17 @@ class ChunkFormerModel:
             sd.pop("encoder.global_cmvn.istd", None)
         model_type = conf.get("model", "asr_model")   # ChunkFormerConfig default (chunkformer_model.py:47-48)
         vocab = int(conf.get("output_dim", sd["ctc.ctc_lo.weight"].shape[0] if "ctc.ctc_lo.weight" in sd else 0))
+        if model_type == "classification":
+            vocab = 0   # init_model.py:77
         cfg = EncoderConfig.from_encoder_conf(conf.get("encoder_conf", {}), input_dim=int(conf.get("input_dim", 80)),
                                               output_dim=vocab, cmvn=has_cmvn)
         rnnt_cfg = RNNTConfig.from_conf(conf, vocab, cfg.d_model) if model_type == "transducer" else None
+        cls_cfg = ClassifierConfig.from_conf(conf, cfg.d_model) if model_type == "classification" else None
+        label_mapping = None
+        lp = os.path.join(path, "label_mapping.json")
+        if os.path.exists(lp):
+            with open(lp) as f:
+                label_mapping = json.load(f)
         char_dict = None
         vp = os.path.join(path, "vocab.txt")
         if os.path.exists(vp):
@@ -290,7 +327,25 @@ class ChunkFormerModel:
                         raise AssertionError(f"bad vocab line {line!r}")
                     char_dict[int(arr[1])] = arr[0]
         return cls(cfg, sd, dtype=dtype, device=device, char_dict=char_dict, fbank_conf=conf.get("fbank_conf"),
-                   resample_conf=conf.get("resample_conf"), model_type=model_type, rnnt_config=rnnt_cfg)
+                   resample_conf=conf.get("resample_conf"), model_type=model_type, rnnt_config=rnnt_cfg,
+                   classifier_config=cls_cfg, label_mapping=label_mapping)
+
+    def get_tasks(self) -> Optional[Dict[str, int]]:
+        """chunkformer_model.py:250-254: {task: classes} of a classification model, else None."""
+        return dict(self.classifier.cfg.tasks) if self.is_classification else None
+
+    def get_classification_heads(self) -> Optional[ClassifierHeads]:
+        """chunkformer_model.py:244-248: the heads of a classification model, else None."""
+        return self.classifier if self.is_classification else None
+
+    def _require_classification(self) -> None:
+        if not self.is_classification:   # chunkformer_model.py:595-598
+            raise ValueError("This model is not a classification model. Use ASR decoding methods instead.")
+
+    def _require_asr(self, what: str) -> None:
+        if self.is_classification:
+            raise ValueError(f"This model is a classification model: {what} needs an asr_model or transducer "
+                             "checkpoint. Use classify / classify_audio / batch_classify instead.")
 
     # ---------------------------------------------------------------- API
     def encode(self, xs: torch.Tensor, xs_lens: torch.Tensor, chunk_size: Optional[int] = None,
@@ -320,6 +375,7 @@ class ChunkFormerModel:
         (EndlessGraphPipeline), without it every call is launched eagerly (EndlessPipeline).  pipeline=False: one segment at a time, the full-size
         middle segments replaying one captured graph (EndlessGraphRunner) when `cuda_graph`.  Every
         mode gives the same result as the eager loop (same kernels, same plans); see streaming.py."""
+        self._require_asr("endless_decode")
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -410,6 +466,7 @@ class ChunkFormerModel:
                      total_batch_duration: int = 1800):
         """chunkformer_model.py:462-552 (asr_model branch): budget grouping, one masked-batch
         encoder call per group, CTC argmax, per-utterance split to its subsampled length."""
+        self._require_asr("batch_decode")
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -446,6 +503,98 @@ class ChunkFormerModel:
             else:
                 decodes.extend(h.flatten()[:n].long() for h, n in zip(hyp.split(n_chunks, dim=0), el_ctc))
         return decodes
+
+    # ---------------------------------------------------------------- classification
+    def _classify_rows(self, enc_rows: torch.Tensor, row_start, row_len):
+        """One cfm_cls_classify call over packed encoder rows -> (pred [B, n_tasks], prob [B, n_tasks])."""
+        pooled, logits, pred, prob = self.classifier.classify(enc_rows, row_start, row_len)
+        self.last_classification = (pooled, logits)   # embeddings and logits of the last call, on the device
+        return pred, prob
+
+    def _label_dicts(self, pred: torch.Tensor, prob: torch.Tensor) -> List[dict]:
+        """chunkformer_model.py:616-640 per utterance: {task: {"label", "label_id", "prob"}}, the label
+        looked up in label_mapping[task] by str(label_id), falling back to the id string."""
+        pred_h, prob_h = pred.cpu().tolist(), prob.cpu().tolist()
+        out = []
+        for ids, ps in zip(pred_h, prob_h):
+            item = {}
+            for task, label_id, p in zip(self.classifier.cfg.task_names, ids, ps):
+                label = str(label_id)
+                if self.label_mapping and task in self.label_mapping:
+                    label = self.label_mapping[task].get(str(label_id), str(label_id))
+                item[task] = {"label": label, "label_id": int(label_id), "prob": float(p)}
+            out.append(item)
+        return out
+
+    @torch.no_grad()
+    def classify(self, xs: torch.Tensor, xs_lens: torch.Tensor, chunk_size: int = -1, left_context_size: int = -1,
+                 right_context_size: int = -1) -> Dict[str, torch.Tensor]:
+        """SpeechClassificationModel.classify (classification_model.py:232-281) on a padded batch
+        xs [B, T, 80]: encoder (any negative context argument = full attention, encoder.py:490-493),
+        mean over each utterance's calc_length(len) valid frames, heads.  Returns
+        {task}_prediction (int64 [B]) and {task}_probability (f32 [B]) on the device.  Pooling and
+        heads run in f32 whatever the encoder dtype (the reference: under its autocast)."""
+        self._require_classification()
+        C, L, R = int(chunk_size), int(left_context_size), int(right_context_size)
+        if C < 0 or L < 0 or R < 0:
+            C = L = R = 0
+        out, masks = self.encoder.forward_encoder(xs, xs_lens, C, L, R)
+        B, Tp, d = out.shape
+        lens = masks.squeeze(1).sum(-1).tolist()
+        pred, prob = self._classify_rows(out.reshape(B * Tp, d), [b * Tp for b in range(B)], lens)
+        res = {}
+        for t, task in enumerate(self.classifier.cfg.task_names):
+            res[f"{task}_prediction"] = pred[:, t].long()
+            res[f"{task}_probability"] = prob[:, t].contiguous()
+        return res
+
+    @torch.no_grad()
+    def classify_audio(self, audio_path: Features, chunk_size: Optional[int] = -1,
+                       left_context_size: Optional[int] = -1, right_context_size: Optional[int] = -1) -> dict:
+        """chunkformer_model.py:555-640: one input (a .wav path or fbank features, as _load_features
+        takes them) -> {task: {"label", "label_id", "prob"}}."""
+        self._require_classification()
+        xs = _load_features(audio_path, self.extract_features)
+        C = -1 if chunk_size is None else chunk_size
+        L = -1 if left_context_size is None else left_context_size
+        R = -1 if right_context_size is None else right_context_size
+        res = self.classify(xs.unsqueeze(0), torch.tensor([xs.shape[0]]), C, L, R)
+        names = self.classifier.cfg.task_names
+        pred = torch.stack([res[f"{t}_prediction"] for t in names], dim=1)
+        prob = torch.stack([res[f"{t}_probability"] for t in names], dim=1)
+        return self._label_dicts(pred, prob)[0]
+
+    @torch.no_grad()
+    def batch_classify(self, audio_paths: List[Features], chunk_size: Optional[int] = 64,
+                       left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
+                       total_batch_duration: int = 1800) -> List[dict]:
+        """Many inputs of uneven length on the masked batch (the bin/classify.py use case): the
+        duration-budget grouping of batch_decode, one forward_parallel_chunk call and one
+        cfm_cls_classify call per group -- utterance b is rows [cumsum(n_chunks)[b] * chunk_size,
+        + calc_length(len_b)) of the packed encoder output, pooled and classified on the device
+        without unpacking.  Returns one {task: {"label", "label_id", "prob"}} dict per input, in
+        input order."""
+        self._require_classification()
+        C = chunk_size if chunk_size is not None else 64
+        L = left_context_size if left_context_size is not None else 128
+        R = right_context_size if right_context_size is not None else 128
+        feats = [_load_features(a, self.extract_features) for a in audio_paths]
+        results: List[dict] = []
+        for grp in budget_groups([f.shape[0] for f in feats], total_batch_duration):
+            xs = [feats[i] for i in grp]
+            lens = torch.tensor([x.shape[0] for x in xs], dtype=torch.int)
+            offset = torch.zeros(len(xs), dtype=torch.int)
+            eo, el, n_chunks, _, _, _ = self.encoder.forward_parallel_chunk(xs, lens, C, L, R, offset=offset)
+            el = [int(n) for n in el.tolist()]
+            for i, n in zip(grp, el):
+                if n <= 0:
+                    what = audio_paths[i] if isinstance(audio_paths[i], str) else f"input {i}"
+                    raise ValueError(f"{what}: {feats[i].shape[0]} frames are too few to classify "
+                                     "(no encoder frame after subsampling)")
+            starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+            pred, prob = self._classify_rows(eo.reshape(-1, eo.shape[-1]), starts, el)
+            results.extend(self._label_dicts(pred, prob))
+        return results
 
 
 def _cmvn_from_stats(mean_stat, var_stat, count):

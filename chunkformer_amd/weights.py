@@ -96,6 +96,21 @@ def synthetic_state_dict(cfg: EncoderConfig, seed: int = 0) -> "OrderedDict[str,
     return sd
 
 
+def synthetic_classifier_state_dict(cfg: EncoderConfig, tasks: Dict[str, int], seed: int = 0,
+                                    scale: float = 1.0) -> "OrderedDict[str, torch.Tensor]":
+    """Encoder weights of `synthetic_state_dict` (no CTC head: a classification model has none,
+    init_model.py:77) plus one `classification_heads.<task>.linear.{weight,bias}` pair per task with
+    the reference ClassificationHead's default Linear init U(+-1/sqrt(d)), times `scale`."""
+    import dataclasses
+    sd = synthetic_state_dict(dataclasses.replace(cfg, vocab=0), seed)
+    g = torch.Generator().manual_seed(seed + 7919)
+    a = scale / math.sqrt(cfg.d_model)
+    for name, n in tasks.items():
+        sd[f"classification_heads.{name}.linear.weight"] = (torch.rand(int(n), cfg.d_model, generator=g) * 2 - 1) * a
+        sd[f"classification_heads.{name}.linear.bias"] = (torch.rand(int(n), generator=g) * 2 - 1) * a
+    return sd
+
+
 def check_state_dict(cfg: EncoderConfig, sd: Dict[str, torch.Tensor]) -> None:
     """Raise if a required key is missing or mis-shaped (load_checkpoint is
     strict=False in the reference, checkpoint.py:26-41, but the kernels need

@@ -307,6 +307,48 @@ int32_t cfm_rnnt_grid_blocks(const cfm_rnnt* h, int32_t B);
  * stopped early and its output is incomplete); -1 if the word could not be read.  Synchronous. */
 int32_t cfm_rnnt_error(const cfm_rnnt* h, const void* workspace, int32_t rows);
 
+/* ---- classification consumer (model: classification checkpoints): masked mean pool over time of the
+ * encoder output and the per-task linear heads, the reference's SpeechClassificationModel
+ * _average_pooling + classify (modules/classification_model.py:174-200, 232-281), on packed rows:
+ * utterance b = rows [row_start[b], row_start[b] + row_len[b]) of enc_dev [rows, d] f32 (device int32
+ * row arrays as in cfm_ctc_collapse; regions must not overlap, gaps between them are never read).
+ *   pooled[b, :] = sum of the utterance's rows / (row_len[b] + 1e-10f)      (zeros when row_len[b] == 0)
+ *   logits[b, :] = W . pooled[b] + bias      W [sum_classes, d]: the tasks' Linear weights stacked in task order
+ *   per task: pred = argmax (lowest index on ties), prob = softmax(logits_task)[pred]
+ * Pooling and heads compute in f32 whatever the encoder's compute dtype (the reference runs the heads
+ * under its fp16 autocast; this is the more exact of the two).  The summation order is fixed (no
+ * floating-point atomics): two calls on the same input are bit-identical.  The pool and classify calls
+ * perform no allocation and no host synchronisation (graph-capturable); their launch geometry follows
+ * from rows and B alone.  d: a multiple of 4 up to 1024.  Limits (CFM_ERR_VALUE beyond): 1 to 16 tasks,
+ * 1 to 1024 classes per task, 4096 classes in total. */
+typedef struct {
+  int32_t enc_dim;          /* the encoder's d_model */
+  int32_t n_tasks;          /* len(model_conf.tasks) */
+  int32_t num_classes[16];  /* in the order of model_conf.tasks */
+} cfm_cls_config;
+typedef struct cfm_cls cfm_cls;
+
+/* weights: 2 * n_tasks views in task order, {weight [num_classes, enc_dim], bias [num_classes]} per task,
+ * i.e. the reference keys classification_heads.<task>.linear.weight / .bias for the tasks of
+ * model_conf.tasks in their order (the caller builds the keys; names are used in error messages only).
+ * A missing or mis-sized view -> CFM_ERR_VALUE. */
+cfm_status cfm_cls_create(const cfm_cls_config* cfg, const cfm_tensor_view* weights, int32_t n_weights,
+                          int32_t device, cfm_cls** out);
+void cfm_cls_destroy(cfm_cls* h);
+/* workspace: int32 slab offsets [B + 1] (256-byte padded), then (ceil(rows / 64) + B) partial column
+ * sums of d floats (one per 64-row slab of an utterance) */
+size_t cfm_cls_pool_workspace_bytes(int32_t rows, int32_t d, int32_t B);
+size_t cfm_cls_workspace_bytes(const cfm_cls* h, int32_t rows, int32_t B);
+/* pooling alone (embeddings), on the current device; needs no handle.  pooled_dev [B, d] f32. */
+cfm_status cfm_cls_pool(const float* enc_dev, int32_t rows, int32_t d, const int32_t* row_start_dev,
+                        const int32_t* row_len_dev, int32_t B, float* pooled_dev, void* workspace,
+                        size_t workspace_bytes, cfm_stream stream);
+cfm_status cfm_cls_classify(const cfm_cls* h, const float* enc_dev, int32_t rows, const int32_t* row_start_dev,
+                            const int32_t* row_len_dev, int32_t B, float* pooled_dev /* [B, d] or NULL */,
+                            float* logits_dev /* [B, sum_classes] or NULL */, int32_t* pred_dev /* [B, n_tasks] */,
+                            float* prob_dev /* [B, n_tasks] f32 */, void* workspace, size_t workspace_bytes,
+                            cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
