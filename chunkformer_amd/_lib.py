@@ -77,6 +77,15 @@ cfm_ctc_logprobs = _sig("cfm_ctc_logprobs", I32, P, P, I32, P, P, P, SZ, P)
 cfm_ctc_ids_workspace_bytes = _sig("cfm_ctc_ids_workspace_bytes", SZ, P, I32)
 cfm_ctc_ids = _sig("cfm_ctc_ids", I32, P, P, I32, P, P, SZ, P)
 cfm_ctc_collapse = _sig("cfm_ctc_collapse", I32, P, P, P, I32, I32, I32, P, P, P, P, P, P)
+# CTC prefix beam search (include/cfm.h)
+cfm_ctc_topk_workspace_bytes = _sig("cfm_ctc_topk_workspace_bytes", SZ, P, I32, I32)
+cfm_ctc_topk_slab_rows = _sig("cfm_ctc_topk_slab_rows", I32, P)
+cfm_ctc_topk = _sig("cfm_ctc_topk", I32, P, P, I32, I32, P, P, P, SZ, P)
+cfm_ctc_topk_logp = _sig("cfm_ctc_topk_logp", I32, P, I32, I32, I32, P, P, P)
+cfm_ctx_create = _sig("cfm_ctx_create", I32, I32, P, P, P, P, I32, P, P, P, I32, ctypes.POINTER(P))
+cfm_ctx_destroy = _sig("cfm_ctx_destroy", None, P)
+cfm_ctc_beam_workspace_bytes = _sig("cfm_ctc_beam_workspace_bytes", SZ, I32, I32, I32, I32, I32)
+cfm_ctc_beam_search = _sig("cfm_ctc_beam_search", I32, P, P, I32, I32, P, P, I32, I32, P, P, P, P, P, P, P, SZ, P)
 # Kaldi fbank (include/cfm.h)
 class CfmFbankConfig(ctypes.Structure):
     _fields_ = [("sample_frequency", ctypes.c_float), ("frame_length_ms", ctypes.c_float),
@@ -138,7 +147,9 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_rnnt_create", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
             "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error",
             "cfm_cls_create", "cfm_cls_destroy", "cfm_cls_pool_workspace_bytes", "cfm_cls_workspace_bytes",
-            "cfm_cls_pool", "cfm_cls_classify"]
+            "cfm_cls_pool", "cfm_cls_classify",
+            "cfm_ctc_topk_workspace_bytes", "cfm_ctc_topk_slab_rows", "cfm_ctc_topk", "cfm_ctc_topk_logp",
+            "cfm_ctx_create", "cfm_ctx_destroy", "cfm_ctc_beam_workspace_bytes", "cfm_ctc_beam_search"]
 
 
 def profile_read(h):

@@ -202,5 +202,8 @@ int ctc_argmax_f16(const float* enc, int M, const f16* W, const float* bias, int
 int ctc_collapse(const int32_t* ids, const int32_t* row_start, const int32_t* row_len, int B, int blank, int max_sil,
                  int32_t* tok, int32_t* tok_frame, int32_t* n_tok, int32_t* seg, int32_t* n_seg, hipStream_t st);
 int log_softmax_rows(float* logits, int M, int V, int write_logp, int32_t* ids, hipStream_t st);
+// per-row top-k (ctc_beam.hip): the k largest x - lse (with_lse: lse as log_softmax_rows forms it) or x,
+// by value descending, index ascending, into vals / ids [M, k]; x is only read
+int ctc_topk_rows(const float* x, int M, int V, int k, int with_lse, float* vals, int32_t* ids, hipStream_t st);
 
 }  // namespace cfm

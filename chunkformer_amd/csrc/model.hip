@@ -175,6 +175,10 @@ struct cfm_model {
   virtual size_t ctc_ws_bytes(int rows) const = 0;
   // ids-only CTC (logp == nullptr): 0 bytes on the fused argmax path
   virtual size_t ctc_ids_ws_bytes(int rows) const = 0;
+  virtual int topk_slab_rows() const = 0;
+  virtual size_t ctc_topk_ws_bytes(int rows) const = 0;
+  virtual cfm_status ctc_topk(const float* enc, int rows, int k, float* vals, int32_t* ids, void* ws, size_t wsb,
+                              hipStream_t st) const = 0;
 };
 
 namespace cfm {
@@ -502,6 +506,16 @@ struct ModelT : public cfm_model {
       }
     }
     if (wsb < ctc_ws_bytes(rows)) return set_error(CFM_ERR_VALUE, "ctc workspace too small");
+    float* dst = nullptr;
+    { const cfm_status hs = head_logits(enc, rows, logp, ws, st, &dst); if (hs != CFM_OK) return hs; }
+    PROF(PC_CTC, log_softmax_rows(dst, rows, V, logp ? 1 : 0, ids, st));
+    return CFM_OK;
+  }
+
+  // the head GEMM: logits = enc . W^T + b over `rows` rows, into logp or (logp == nullptr) the logit
+  // buffer at the start of the workspace (ctc_ws_bytes(rows)); *out = where they went
+  cfm_status head_logits(const float* enc, int rows, float* logp, void* ws, hipStream_t st, float** out) const {
+    const int d = cfg.d_model, V = cfg.vocab;
     Carver c(ws);
     float* logits = c.take<float>((size_t)rows * V);
     T* a = c.take<T>((size_t)rows * d);
@@ -513,6 +527,7 @@ struct ModelT : public cfm_model {
       A = a;
     }
     float* dst = logp ? logp : logits;
+    *out = dst;
     // the vocabulary splits into a 256-multiple part (256 x 256 MFMA tiles) and a remainder (128 x 128
     // tiles); f32x4 epilogue stores need the row pitch V % 4 == 0
     const int V1 = (sizeof(T) == 2 && V % 4 == 0) ? V / 256 * 256 : 0;
@@ -524,7 +539,30 @@ struct ModelT : public cfm_model {
       EpiArgs e = E(); e.bias = fe.ctc_b + V1; e.out = dst + V1; e.ldo = V;
       PROF(PC_CTC, gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, (const T*)fe.ctc_w + (size_t)V1 * d, d, rows, V - V1, d, e, st));
     }
-    PROF(PC_CTC, log_softmax_rows(dst, rows, V, logp ? 1 : 0, ids, st));
+    return CFM_OK;
+  }
+
+  // per-frame top-k of the CTC log-probs (cfm_ctc_topk): row slabs bound the logit workspace
+  int topk_slab_rows() const override {
+    if (cfg.vocab <= 0) return 0;
+    // at most 16384 rows (64 row tiles of 256: V = 5000 gives 1280 head-GEMM tiles, five full rounds of
+    // 256 CUs) and at most 512 MiB of logits
+    const size_t r = (((size_t)512 << 20) / ((size_t)cfg.vocab * sizeof(float))) / 256 * 256;
+    return (int)std::min<size_t>(16384, std::max<size_t>(256, r));
+  }
+  size_t ctc_topk_ws_bytes(int rows) const override { return ctc_ws_bytes(std::min(rows, topk_slab_rows())); }
+  cfm_status ctc_topk(const float* enc, int rows, int k, float* vals, int32_t* ids, void* ws, size_t wsb,
+                      hipStream_t st) const override {
+    if (!fe.ctc_w) return set_error(CFM_ERR_ASSERT, "model has no CTC head (vocab == 0)");
+    const int d = cfg.d_model, V = cfg.vocab, slab = topk_slab_rows();
+    if (k < 1 || k > 16 || k > V) return set_error(CFM_ERR_VALUE, "top-k: 1 <= k <= 16 and k <= vocab");
+    if (wsb < ctc_topk_ws_bytes(rows)) return set_error(CFM_ERR_VALUE, "ctc top-k workspace too small");
+    for (int r0 = 0; r0 < rows; r0 += slab) {
+      const int nr = std::min(slab, rows - r0);
+      float* logits = nullptr;
+      { const cfm_status hs = head_logits(enc + (size_t)r0 * d, nr, nullptr, ws, st, &logits); if (hs != CFM_OK) return hs; }
+      PROF(PC_CTC, ctc_topk_rows(logits, nr, V, k, 1, vals + (size_t)r0 * k, ids + (size_t)r0 * k, st));
+    }
     return CFM_OK;
   }
 };
@@ -1038,6 +1076,21 @@ cfm_status cfm_ctc_logprobs(const cfm_model* m, const float* enc, int32_t rows, 
   if (rows <= 0) return CFM_OK;
   HIPC(hipSetDevice(m->device));
   return m->ctc(enc, rows, logp, ids, ws, wsb, (hipStream_t)stream);
+}
+
+size_t cfm_ctc_topk_workspace_bytes(const cfm_model* m, int32_t rows, int32_t k) {
+  (void)k;
+  return m && rows > 0 ? m->ctc_topk_ws_bytes(rows) : 0;
+}
+
+int32_t cfm_ctc_topk_slab_rows(const cfm_model* m) { return m ? m->topk_slab_rows() : 0; }
+
+cfm_status cfm_ctc_topk(const cfm_model* m, const float* enc, int32_t rows, int32_t k, float* topk_logp,
+                        int32_t* topk_ids, void* ws, size_t wsb, cfm_stream stream) {
+  if (!m || !enc || !topk_logp || !topk_ids) return set_error(CFM_ERR_VALUE, "null argument");
+  if (rows < 0) return set_error(CFM_ERR_VALUE, "rows < 0");
+  HIPC(hipSetDevice(m->device));
+  return m->ctc_topk(enc, rows, k, topk_logp, topk_ids, ws, wsb, (hipStream_t)stream);
 }
 
 size_t cfm_ctc_ids_workspace_bytes(const cfm_model* m, int32_t rows) { return m ? m->ctc_ids_ws_bytes(rows) : 0; }

@@ -442,6 +442,42 @@ class ChunkFormerEncoder:
         return (logp.view(*shape, -1) if logp is not None else None), (ids.view(*shape) if ids is not None else None)
 
     @torch.no_grad()
+    def ctc_topk(self, hs: torch.Tensor, k: int):
+        """Per-frame top-k of log_softmax(ctc_lo(hs)) (cfm_ctc_topk): values [..., k] f32 and ids
+        [..., k] int32, by value descending, index ascending.  The log-prob tensor is never written;
+        the head GEMM runs in row slabs of `ctc_topk_slab_rows()`."""
+        if self.cfg.vocab <= 0:
+            raise AssertionError("model has no CTC head")
+        k = int(k)
+        if not 1 <= k <= 16 or k > self.cfg.vocab:
+            raise ValueError(f"top-k {k}: 1 .. 16 and at most the vocabulary ({self.cfg.vocab})")
+        shape = hs.shape[:-1]
+        enc = hs.reshape(-1, self.cfg.d_model).to(self.device, torch.float32).contiguous()
+        rows = enc.shape[0]
+        vals = torch.empty(rows, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(rows, k, dtype=torch.int32, device=self.device)
+        if rows > 0:
+            nbytes = int(_lib.cfm_ctc_topk_workspace_bytes(self._h, rows, k))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(_lib.cfm_ctc_topk(self._h, enc.data_ptr(), rows, k, vals.data_ptr(), ids.data_ptr(),
+                                         ws.data_ptr(), nbytes, self._stream()))
+        return vals.view(*shape, k), ids.view(*shape, k)
+
+    def ctc_topk_slab_rows(self) -> int:
+        return int(_lib.cfm_ctc_topk_slab_rows(self._h))
+
+    @torch.no_grad()
+    def ctc_prefix_beam_search(self, hs_rows: torch.Tensor, row_start, row_len, beam_size: int = 10,
+                               context_graph=None, blank_id: int = 0, with_times: bool = True):
+        """CTC prefix beam search (modules/search.py:131-249) over packed encoder rows [rows, d]:
+        utterance b = rows [row_start[b], row_start[b] + row_len[b]).  The top-k kernel, then one beam
+        kernel launch with one workgroup per utterance -> List[DecodeResult]."""
+        from .search import beam_search_topk_device
+        vals, ids = self.ctc_topk(hs_rows.reshape(-1, self.cfg.d_model), beam_size)
+        return beam_search_topk_device(vals, ids, row_start, row_len, int(beam_size), context_graph, blank_id,
+                                       with_times)
+
+    @torch.no_grad()
     def ctc_collapse(self, ids: torch.Tensor, row_start, row_len, max_silence: Optional[int] = None,
                      blank_id: int = 0):
         """CTC post-processing on device over utterance b = ids[row_start[b] : row_start[b] + row_len[b]].

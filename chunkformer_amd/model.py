@@ -347,6 +347,18 @@ class ChunkFormerModel:
             raise ValueError(f"This model is a classification model: {what} needs an asr_model or transducer "
                              "checkpoint. Use classify / classify_audio / batch_classify instead.")
 
+    def _beam_method(self, decoding_method: str) -> bool:
+        """True for "ctc_prefix_beam_search" (CTC checkpoints only), False for the greedy default."""
+        if decoding_method == "ctc_greedy_search":
+            return False
+        if decoding_method != "ctc_prefix_beam_search":
+            raise ValueError(f"unknown decoding_method {decoding_method!r}: ctc_greedy_search or "
+                             "ctc_prefix_beam_search")
+        if self.model_type == "transducer":
+            raise ValueError("This model is a transducer model: ctc_prefix_beam_search needs an asr_model "
+                             "checkpoint. Its decoding is the RNN-T greedy search.")
+        return True
+
     # ---------------------------------------------------------------- API
     def encode(self, xs: torch.Tensor, xs_lens: torch.Tensor, chunk_size: Optional[int] = None,
                left_context_size: Optional[int] = None, right_context_size: Optional[int] = None, **kwargs):
@@ -361,7 +373,8 @@ class ChunkFormerModel:
                        total_batch_duration: int = 1800, return_timestamps: bool = True,
                        max_silence_duration: float = 0.5, return_encoder_out: bool = False,
                        cuda_graph: bool = True, pipeline: Optional[bool] = None,
-                       pipeline_depth: Optional[int] = None):
+                       pipeline_depth: Optional[int] = None, decoding_method: str = "ctc_greedy_search",
+                       beam_size: int = 10, context_graph=None, return_nbest: bool = False):
         """chunkformer_model.py:321-459.  Segments of `total_batch_duration` seconds (halved,
         like the reference) go through forward_parallel_chunk with the attention/conv caches
         and `offset` carried; the CTC argmax runs per segment on the kept rows (row-wise, so
@@ -374,8 +387,13 @@ class ChunkFormerModel:
         segments (up to 128 per graph) replay one captured HIP graph of that whole multi-stream pipeline
         (EndlessGraphPipeline), without it every call is launched eagerly (EndlessPipeline).  pipeline=False: one segment at a time, the full-size
         middle segments replaying one captured graph (EndlessGraphRunner) when `cuda_graph`.  Every
-        mode gives the same result as the eager loop (same kernels, same plans); see streaming.py."""
+        mode gives the same result as the eager loop (same kernels, same plans); see streaming.py.
+        decoding_method "ctc_prefix_beam_search": the runner returns the encoder rows, and the top-k and
+        beam kernels run over their concatenation as one utterance (`beam_size`, `context_graph`); the
+        sentence split then places the best hypothesis' tokens at their `times` frames.
+        `return_nbest`: the n-best texts (or the DecodeResult without a char_dict)."""
         self._require_asr("endless_decode")
+        beam = self._beam_method(decoding_method)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -386,7 +404,7 @@ class ChunkFormerModel:
         ids, outs = [], []
         seg_len = max(stop - start for start, stop, _, _ in segs) if segs else 0
         transducer = self.model_type == "transducer"
-        want_eo = bool(return_encoder_out) or transducer   # the RNN-T search consumes the encoder rows
+        want_eo = bool(return_encoder_out) or transducer or beam   # the searches consume the encoder rows
         if pipeline is None:
             pipeline = len(segs) >= 3
         if pipeline_depth is None:
@@ -445,6 +463,26 @@ class ChunkFormerModel:
             if return_encoder_out:
                 return res, enc_all.unsqueeze(0)
             return res
+        if beam:
+            enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
+            T = enc_all.shape[0]
+            best = enc.ctc_prefix_beam_search(enc_all, [0], [T], beam_size, context_graph)[0]
+            if self.char_dict is None:
+                res = best
+            elif return_nbest:
+                res = [class2str(h, self.char_dict).strip() for h in best.nbest]
+            else:
+                # the reference's sentence split over a dense [T, 1] array with the best hypothesis' tokens
+                # at their Viterbi frames (no duplicate removal: "a a" stays two tokens)
+                dense = np.zeros((T, 1), dtype=np.int64)
+                dense[np.asarray(best.times, dtype=np.int64), 0] = np.asarray(best.tokens, dtype=np.int64)
+                res = format_segments(transducer_segments(dense, max_silence_frames(max_silence_duration)),
+                                      self.char_dict)
+                if not return_timestamps:
+                    res = " ".join(item["decode"] for item in res).strip()
+            if return_encoder_out:
+                return res, enc_all.unsqueeze(0)
+            return res
         tokens = torch.cat(ids).long().reshape(1, -1, 1) if ids else None
         if self.char_dict is not None and tokens is not None:
             # get_output_with_timestamps (model_utils.py:174-221) on the device: sentence split at
@@ -463,10 +501,15 @@ class ChunkFormerModel:
     @torch.no_grad()
     def batch_decode(self, audio_paths: List[Features], chunk_size: Optional[int] = 64,
                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
-                     total_batch_duration: int = 1800):
+                     total_batch_duration: int = 1800, decoding_method: str = "ctc_greedy_search",
+                     beam_size: int = 10, context_graph=None, return_nbest: bool = False):
         """chunkformer_model.py:462-552 (asr_model branch): budget grouping, one masked-batch
-        encoder call per group, CTC argmax, per-utterance split to its subsampled length."""
+        encoder call per group, CTC argmax, per-utterance split to its subsampled length.
+        decoding_method "ctc_prefix_beam_search": one top-k and one beam-search call per masked batch over
+        the same per-utterance row ranges (`beam_size`, `context_graph`: search.ContextGraph); text of the
+        best hypothesis (`return_nbest`: of every hypothesis), or DecodeResults without a char_dict."""
         self._require_asr("batch_decode")
+        beam = self._beam_method(decoding_method)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -493,6 +536,17 @@ class ChunkFormerModel:
                     decodes.extend(class2str(h, self.char_dict).strip() for h in hyps)
                 else:
                     decodes.extend(hyps)
+                continue
+            if beam:
+                starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+                for r in self.encoder.ctc_prefix_beam_search(eo.reshape(-1, eo.shape[-1]), starts, el_ctc, beam_size,
+                                                             context_graph):
+                    if self.char_dict is None:
+                        decodes.append(r)
+                    elif return_nbest:
+                        decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
+                    else:
+                        decodes.append(class2str(r.tokens, self.char_dict).strip())
                 continue
             _, hyp = self.encoder.ctc_log_softmax(eo, want_logp=False)   # fused argmax head
             if self.char_dict is not None:

@@ -222,6 +222,48 @@ cfm_status cfm_ctc_collapse(const int32_t* ids_dev, const int32_t* row_start_dev
                             int32_t* n_tokens_dev, int32_t* segments_dev /* [rows, 3] or NULL */,
                             int32_t* n_segments_dev /* [B] or NULL */, cfm_stream stream);
 
+/* ---- CTC prefix beam search (modules/search.py:131-249 with score = log_add([s, ns]); hotword
+ * biasing: utils/context_graph.py).
+ *
+ * Per-frame top-k of the CTC log-probs over enc_dev [rows, d]: the k largest logit - lse of every row
+ * (lse as CTC.log_softmax forms it), ordered by value descending, index ascending.  The head GEMM runs
+ * in row slabs inside the call, so the logit workspace is bounded whatever `rows` is, and no [rows, V]
+ * log-prob tensor is written.  1 <= k <= 16, k <= V.  No allocation, no host synchronisation. */
+size_t cfm_ctc_topk_workspace_bytes(const cfm_model* m, int32_t rows, int32_t k);
+int32_t cfm_ctc_topk_slab_rows(const cfm_model* m);
+cfm_status cfm_ctc_topk(const cfm_model* m, const float* enc_dev, int32_t rows, int32_t k,
+                        float* topk_logp_dev /* [rows, k] */, int32_t* topk_ids_dev /* [rows, k] */,
+                        void* workspace, size_t workspace_bytes, cfm_stream stream);
+/* The same selection over log-probs logp_dev [rows, V] f32 given directly (on the current device). */
+cfm_status cfm_ctc_topk_logp(const float* logp_dev, int32_t rows, int32_t V, int32_t k, float* topk_logp_dev,
+                             int32_t* topk_ids_dev, cfm_stream stream);
+
+/* Biasing graph: flat HOST arrays of an Aho-Corasick graph with n_nodes nodes (root = 0, ids in
+ * creation order): per node the fail arc and the token / node / output scores; n_trans transitions
+ * (node, token, next) sorted by (node, token). */
+typedef struct cfm_ctx cfm_ctx;
+cfm_status cfm_ctx_create(int32_t n_nodes, const int32_t* fail_host, const double* token_score_host,
+                          const double* node_score_host, const double* output_score_host, int32_t n_trans,
+                          const int32_t* trans_node_host, const int32_t* trans_token_host,
+                          const int32_t* trans_next_host, int32_t device, cfm_ctx** out);
+void cfm_ctx_destroy(cfm_ctx* h);
+
+/* The search over packed top-k rows [rows, k], one workgroup per utterance b = rows
+ * [row_start[b], row_start[b] + row_len[b]) as in cfm_ctc_collapse; nothing synchronises between
+ * workgroups.  Hypothesis n of utterance b is written compacted at out_*[n, row_start[b] ..];
+ * out_len / out_score [B, k] (score = total score after finalize, f64), n_hyps [B] (fewer than k
+ * hypotheses can exist; row_len == 0 gives one empty hypothesis with score 0).  out_times_dev NULL: no
+ * times.  The first int32 of the workspace is an error word, zero after a complete search (1: a row
+ * range outside [0, rows); 4: a NaN score, from non-finite log-probs; other values: internal); read it after the stream has completed.  A
+ * workspace smaller than cfm_ctc_beam_workspace_bytes is CFM_ERR_VALUE before anything is launched. */
+size_t cfm_ctc_beam_workspace_bytes(int32_t rows, int32_t B, int32_t k, int32_t with_times, int32_t n_context_nodes);
+cfm_status cfm_ctc_beam_search(const float* topk_logp_dev, const int32_t* topk_ids_dev, int32_t rows, int32_t k,
+                               const int32_t* row_start_dev, const int32_t* row_len_dev, int32_t B, int32_t blank_id,
+                               const cfm_ctx* context /* or NULL */, int32_t* out_tokens_dev /* [k, rows] */,
+                               int32_t* out_times_dev /* [k, rows] or NULL */, int32_t* out_len_dev /* [B, k] */,
+                               double* out_score_dev /* [B, k] */, int32_t* n_hyps_dev /* [B] */, void* workspace,
+                               size_t workspace_bytes, cfm_stream stream);
+
 /* ---- Kaldi log-mel filterbank (the reference's feature front: chunkformer_model.py:276-318 and
  * dataset/processor.py:210-239 call torchaudio.compliance.kaldi.fbank).  Fields and defaults follow
  * torchaudio's fbank() signature; the reference decodes with dither 0, energy_floor 0, 80 bins,
