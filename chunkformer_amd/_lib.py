@@ -86,6 +86,11 @@ cfm_ctx_create = _sig("cfm_ctx_create", I32, I32, P, P, P, P, I32, P, P, P, I32,
 cfm_ctx_destroy = _sig("cfm_ctx_destroy", None, P)
 cfm_ctc_beam_workspace_bytes = _sig("cfm_ctc_beam_workspace_bytes", SZ, I32, I32, I32, I32, I32)
 cfm_ctc_beam_search = _sig("cfm_ctc_beam_search", I32, P, P, I32, I32, P, P, I32, I32, P, P, P, P, P, P, P, SZ, P)
+# CTC forced alignment (include/cfm.h)
+CFM_ALIGN_GENERIC_STRIPS = 1
+cfm_ctc_align_plan = _sig("cfm_ctc_align_plan", SZ, P, P, I32, P)
+cfm_ctc_align = _sig("cfm_ctc_align", I32, P, I32, I32, P, P, I32, I32, P, I32, P, P, P, P, P, P, P, P, P, P, I32, I32, P,
+                     SZ, P)
 # Kaldi fbank (include/cfm.h)
 class CfmFbankConfig(ctypes.Structure):
     _fields_ = [("sample_frequency", ctypes.c_float), ("frame_length_ms", ctypes.c_float),
@@ -149,7 +154,8 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_cls_create", "cfm_cls_destroy", "cfm_cls_pool_workspace_bytes", "cfm_cls_workspace_bytes",
             "cfm_cls_pool", "cfm_cls_classify",
             "cfm_ctc_topk_workspace_bytes", "cfm_ctc_topk_slab_rows", "cfm_ctc_topk", "cfm_ctc_topk_logp",
-            "cfm_ctx_create", "cfm_ctx_destroy", "cfm_ctc_beam_workspace_bytes", "cfm_ctc_beam_search"]
+            "cfm_ctx_create", "cfm_ctx_destroy", "cfm_ctc_beam_workspace_bytes", "cfm_ctc_beam_search",
+            "cfm_ctc_align_plan", "cfm_ctc_align"]
 
 
 def profile_read(h):

@@ -478,6 +478,18 @@ class ChunkFormerEncoder:
                                        with_times)
 
     @torch.no_grad()
+    def ctc_align(self, hs_rows: torch.Tensor, row_start, row_len, targets, blank_id: int = 0,
+                  max_workspace_bytes: Optional[int] = None, return_status: bool = False):
+        """CTC forced alignment (align.py, csrc/ctc_align.hip) of the token-id lists `targets` to packed
+        encoder rows [rows, d]: utterance b = rows [row_start[b], row_start[b] + row_len[b]).  One
+        ctc_log_softmax call and one align call (trellis and backtrace kernels, one workgroup per
+        utterance) -> List[AlignResult]; ValueError names the utterances that cannot be aligned
+        (`return_status`: (results, status per utterance) instead)."""
+        from .align import align_packed
+        logp, _ = self.ctc_log_softmax(hs_rows.reshape(-1, self.cfg.d_model), want_logp=True, want_ids=False)
+        return align_packed(logp, row_start, row_len, targets, blank_id, max_workspace_bytes, return_status)
+
+    @torch.no_grad()
     def ctc_collapse(self, ids: torch.Tensor, row_start, row_len, max_silence: Optional[int] = None,
                      blank_id: int = 0):
         """CTC post-processing on device over utterance b = ids[row_start[b] : row_start[b] + row_len[b]].

@@ -558,6 +558,61 @@ class ChunkFormerModel:
                 decodes.extend(h.flatten()[:n].long() for h, n in zip(hyp.split(n_chunks, dim=0), el_ctc))
         return decodes
 
+    # ---------------------------------------------------------------- forced alignment
+    def _require_ctc_align(self, what: str) -> None:
+        self._require_asr(what)
+        if self.model_type == "transducer":
+            raise ValueError(f"This model is a transducer model: {what} needs an asr_model checkpoint "
+                             "(CTC forced alignment runs on the CTC head's log-probs).")
+
+    @torch.no_grad()
+    def batch_align(self, audio_paths: List[Features], targets, chunk_size: Optional[int] = 64,
+                    left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
+                    total_batch_duration: int = 1800, max_workspace_bytes: Optional[int] = None):
+        """CTC forced alignment of many inputs (the reference: bin/alignment.py, one utterance at a time
+        through torchaudio on the CPU): batch_decode's budget groups and per-utterance row ranges, one
+        masked-batch encoder call, one ctc_log_softmax call and one align call per group.  `targets`:
+        one token-id list per input.  Returns one align.AlignResult per input, in input order (frames,
+        spans, token_times(), words(char_dict)); ValueError names the inputs that cannot be aligned, after
+        the others have been computed.  `max_workspace_bytes` bounds the trellis."""
+        self._require_ctc_align("batch_align")
+        if len(targets) != len(audio_paths):
+            raise ValueError("batch_align needs one target per input")
+        C = chunk_size if chunk_size is not None else 64
+        L = left_context_size if left_context_size is not None else 128
+        R = right_context_size if right_context_size is not None else 128
+        from .align import raise_failed
+        feats = [_load_features(a, self.extract_features) for a in audio_paths]
+        results, status = [None] * len(feats), [0] * len(feats)
+        for grp in budget_groups([f.shape[0] for f in feats], total_batch_duration):
+            xs = [feats[i] for i in grp]
+            lens = torch.tensor([x.shape[0] for x in xs], dtype=torch.int)
+            offset = torch.zeros(len(xs), dtype=torch.int)
+            eo, el, n_chunks, _, _, _ = self.encoder.forward_parallel_chunk(xs, lens, C, L, R, offset=offset)
+            el_ctc = [len(range(int(nc) * C)[: int(n)]) for nc, n in zip(n_chunks, el.tolist())]
+            starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+            res, st = self.encoder.ctc_align(eo.reshape(-1, eo.shape[-1]), starts, el_ctc, [targets[i] for i in grp],
+                                             max_workspace_bytes=max_workspace_bytes, return_status=True)
+            for i, r, code in zip(grp, res, st):
+                results[i], status[i] = r, code
+        raise_failed(status)
+        return results
+
+    @torch.no_grad()
+    def endless_align(self, audio_path: Features, target, chunk_size: Optional[int] = 64,
+                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
+                      total_batch_duration: int = 1800, max_workspace_bytes: Optional[int] = None, **endless_kwargs):
+        """CTC forced alignment of one long recording: the encoder rows of
+        endless_decode(..., return_encoder_out=True) aligned to the token ids `target` as one utterance
+        -> align.AlignResult.  The trellis takes 4 bytes per frame and 16 states (`max_workspace_bytes`
+        raises before anything is launched when it would be larger)."""
+        self._require_ctc_align("endless_align")
+        _, eo = self.endless_decode(audio_path, chunk_size, left_context_size, right_context_size,
+                                    total_batch_duration=total_batch_duration, return_encoder_out=True,
+                                    **endless_kwargs)
+        rows = eo[0]
+        return self.encoder.ctc_align(rows, [0], [rows.shape[0]], [target], max_workspace_bytes=max_workspace_bytes)[0]
+
     # ---------------------------------------------------------------- classification
     def _classify_rows(self, enc_rows: torch.Tensor, row_start, row_len):
         """One cfm_cls_classify call over packed encoder rows -> (pred [B, n_tasks], prob [B, n_tasks])."""

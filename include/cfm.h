@@ -264,6 +264,41 @@ cfm_status cfm_ctc_beam_search(const float* topk_logp_dev, const int32_t* topk_i
                                double* out_score_dev /* [B, k] */, int32_t* n_hyps_dev /* [B] */, void* workspace,
                                size_t workspace_bytes, cfm_stream stream);
 
+/* ---- CTC forced alignment (utils/model_utils.py:103-117 force_align, which the reference runs through
+ * torchaudio.functional.forced_align on the CPU; semantics: DESIGN.md 9c).
+ *
+ * Viterbi alignment of a known target to packed log-probs logp_dev [rows, V] f32 (what cfm_ctc_logprobs
+ * writes), one workgroup per utterance b = rows [row_start[b], row_start[b] + row_len[b]) as in
+ * cfm_ctc_collapse, its target = targets_dev[target_start[b] .. + target_len[b]) (int32, packed,
+ * n_targets in all).  Scores in f64; on exact ties stay, then step, then skip.  Outputs:
+ *   frames_dev [rows] int32      the label of every frame of the utterance's rows (other rows untouched);
+ *   frame_logp_dev [rows] f32    logp[t][frames[t]] (or NULL);
+ *   spans_dev [n_targets, 2]     first and last frame, inclusive and relative to the utterance, of each
+ *                                target token (or NULL);
+ *   score_dev [B] f64            the alignment's log-probability;
+ *   status_dev [B] int32         0 ok; 1 infeasible (row_len < target_len + adjacent repeats); 2 a row or
+ *                                target range outside its array; 3 a target id outside [0, V) or equal to
+ *                                blank_id; 4 end state not finite (NaN / -inf log-probs); 5 the
+ *                                utterance's workspace region lies outside the workspace or the device
+ *                                lengths differ from the host's.  Non-zero: that utterance's other
+ *                                outputs are untouched.
+ * cfm_ctc_align_plan (host only) returns the workspace bytes for the HOST length arrays and writes each
+ * utterance's byte offset into it (upload them as ws_offset_dev): 2-bit backpointers, 4 bytes per frame
+ * and 16 states, plus two alpha rows.  cfm_ctc_align takes the same host arrays again: a workspace
+ * smaller than the plan is CFM_ERR_VALUE before anything is launched.  The alpha rows live in LDS for
+ * utterances of up to lds_max_states states (2 * target_len + 1; negative = the default and maximum,
+ * 8192; 0 = never), else in the workspace (256-byte aligned).  No allocation, no host synchronisation. */
+#define CFM_ALIGN_GENERIC_STRIPS 1 /* flags: the strip loop without per-thread label registers (any length) */
+size_t cfm_ctc_align_plan(const int32_t* row_len_host, const int32_t* target_len_host, int32_t B,
+                          int64_t* ws_offset_host_out /* [B] or NULL */);
+cfm_status cfm_ctc_align(const float* logp_dev, int32_t rows, int32_t V, const int32_t* row_start_dev,
+                         const int32_t* row_len_dev, int32_t B, int32_t blank_id, const int32_t* targets_dev,
+                         int32_t n_targets, const int32_t* target_start_dev, const int32_t* target_len_dev,
+                         const int64_t* ws_offset_dev, const int32_t* row_len_host, const int32_t* target_len_host,
+                         int32_t* frames_dev, float* frame_logp_dev /* or NULL */, int32_t* spans_dev /* or NULL */,
+                         double* score_dev, int32_t* status_dev, int32_t lds_max_states, int32_t flags,
+                         void* workspace, size_t workspace_bytes, cfm_stream stream);
+
 /* ---- Kaldi log-mel filterbank (the reference's feature front: chunkformer_model.py:276-318 and
  * dataset/processor.py:210-239 call torchaudio.compliance.kaldi.fbank).  Fields and defaults follow
  * torchaudio's fbank() signature; the reference decodes with dither 0, energy_floor 0, 80 bins,
