@@ -235,16 +235,10 @@ constexpr int KR_BYTES = RING * 128;            // K ring [384][64] bf16, 16-B c
 constexpr int P_BYTES_ = RING * 128;            // P rows [384][64] bf16, swizzled
 constexpr int VT_PITCH_B = (RING + 8) * 2;      // V^T [64 dims][384 (+8)] bf16
 constexpr int VT_BYTES_ = 64 * VT_PITCH_B;
-#ifndef ATTN_SCR_PITCH
-#define ATTN_SCR_PITCH 49   // sheared skew writes: bf16 per query row (read pitch one less, a multiple of 4)
-#endif
-#ifndef ATTN_RD_PITCH
-#define ATTN_RD_PITCH 52    // ATTN_SKEW_RD: unsheared rows (a multiple of 4: aligned ds_write_b64; 52 = 4 mod 8:
-                            // the 16-lane write groups hit 32 distinct banks)
-#endif
-constexpr int SCR_PITCH = ATTN_SCR_PITCH;       // bf16 per query row of the skew scratch (48-wide band, 4k+1: rel_shift reshape)
-constexpr int RD_PITCH = ATTN_RD_PITCH;
-constexpr int SCR_ELEMS = 16 * SCR_PITCH > 16 * RD_PITCH + 8 ? 16 * SCR_PITCH : 16 * RD_PITCH + 8;
+// bf16 per query row of the skew scratch (48-wide band, rows unsheared): a multiple of 4 (aligned ds_write_b64);
+// 52 = 4 mod 8: the 16-lane write groups hit 32 distinct banks
+constexpr int RD_PITCH = 52;
+constexpr int SCR_ELEMS = 16 * RD_PITCH + 8;
 constexpr int SCR_BYTES = (SCR_ELEMS * 2 + 15) / 16 * 16;   // per wave
 constexpr int RING_LDS = KR_BYTES + P_BYTES_ + VT_BYTES_ + 8 * SCR_BYTES + 512;
 }  // namespace
@@ -260,108 +254,32 @@ CFM_DEV unsigned pack_e2(float a, float b) {
   return __builtin_bit_cast(unsigned, (e2){(E)a, (E)b});
 }
 CFM_DEV int sw128(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
-#ifndef RING_KPF
-#define RING_KPF 0   // ring kernel, interior chunks: next tile's K fragments read before this tile's skew (round 6,
-                     // with the conflict-free skew: off 4.22 vs on 4.30 ms/step, one-process A/B)
-#endif
-#ifndef RING_V4
-#define RING_V4 1   // next-pair staging in row quads (8-B V^T stores, half the store instructions) when W % 4 == 0:
-                    // the staged rows start at flat row c0 C + (cp - c0) C + W + C + 4k = W (mod 4), and a quad must
-                    // not straddle the ring wrap (RING % 4 == 0) nor split an 8-B V^T store; W % 4 == 2 stages in pairs
-#endif
-#ifndef ATTN_PRIO
-#define ATTN_PRIO 1   // static wave priority: 1 = the second-dispatched half (waves 4-7) at s_setprio 1 (ring attention
-                      // 4.82 -> 4.74 ms/step, tools/ab_prio.sh); 2 = waves 0-3 instead (4.77); 0 = none
-#endif
 // the two halves of an 8-wave block are SIMD partners running the same program (MI355X_MICROARCH.md,
-// "Two waves per SIMD" item 4: a static priority for the arbitration loser)
+// "Two waves per SIMD" item 4: a static priority for the arbitration loser): the second-dispatched half
+// (waves 4-7) runs at s_setprio 1 (ring attention 4.82 -> 4.74 ms/step)
 CFM_DEV void attn_static_prio(int half) {
-  if constexpr (ATTN_PRIO == 1) { if (half) __builtin_amdgcn_s_setprio(1); }
-  if constexpr (ATTN_PRIO == 2) { if (!half) __builtin_amdgcn_s_setprio(1); }
-  (void)half;
+  if (half) __builtin_amdgcn_s_setprio(1);
 }
-#ifndef ATTN_SKEW_RD
-#define ATTN_SKEW_RD 1   // ring / dense kernels' rel_shift: 1 = unsheared aligned ds_write_b64 rows at pitch RD_PITCH
-                         // and the shear on the read side (ds_read2_b32 + ds_read_b32 + two v_alignbit per 4 values);
-                         // 0 = sheared ds_write_b16 writes at pitch SCR_PITCH, aligned ds_read_b64 reads
-#endif
 
 // rel_shift of one 32-key half (hh) of a 64-key tile through the wave's bf16 scratch (attention.py:242-266, the
 // reference's pad / reshape trick): b[0..2] = band^T subtiles 2hh .. 2hh+2 (P rows kb0 + 16(2hh+pt) + 4g + rr,
-// query fr); returns in bd[st2] the band of (query fr, keys j0 + 32hh + 16st2 + 4g .. +3) = band column
-// 16st2 + 4g + rr + 15 - fr.  Round 6: with ATTN_SKEW_RD the rows are written unsheared (one aligned
-// ds_write_b64 per subtile) and sheared on the read; the round-5 layout (sheared 2-B writes, pitch 49 / 48)
+// query fr); the result is the band of (query fr, keys j0 + 32hh + 16st2 + 4g .. +3) = band column
+// 16st2 + 4g + rr + 15 - fr.  The rows are written unsheared (one aligned ds_write_b64 per subtile) and sheared
+// on the read (ds_read2_b32 + ds_read_b32 per 4 values); the round-5 layout (sheared 2-B writes, pitch 49 / 48)
 // spent a quarter of the kernel's LDS cycles in 2-way bank conflicts (PMC SQ_LDS_BANK_CONFLICT 25% of
 // SQ_LDS_IDX_ACTIVE; a model of the banking: the b16 writes and the pitch-48 b64 reads are 2-way, pitch-52
 // b64 writes conflict-free, the read-side shear's dword reads 2-way): 112 -> 72 LDS cycles per wave and tile.
-// ATTN_SKEW_PERM: query row fr lives in row slot skew_slot(fr) of the pitch-52 scratch.  With rows in query
+// Query row fr lives in row slot skew_slot(fr) of the pitch-52 scratch.  With rows in query
 // order the reads' first dwords (2 q(fr) + (15 - fr) / 2 for slot q(fr) in 8-B units) and those 2 banks on (g odd)
 // collide pairwise in the 32-lane groups; a permutation whose slots keep q mod 16 distinct (the writes stay
 // conflict-free) and make those 32 dwords distinct mod 32 removes the reads' conflicts: 72 -> 60 cycles per wave
 // and tile in the model (the permutation is one solution of that search; any slot order keeps the layout valid)
-#ifndef ATTN_SKEW_PERM
-#define ATTN_SKEW_PERM 1
-#endif
 CFM_DEV int skew_slot(int fr) {
-  if constexpr (ATTN_SKEW_PERM && ATTN_SKEW_RD) return (int)((0x9f35c268b17de4a0ull >> (4 * fr)) & 15u);
-  return fr;
+  return (int)((0x9f35c268b17de4a0ull >> (4 * fr)) & 15u);
 }
-template <typename E>
-CFM_DEV void skew_half(unsigned scr_base, int fr, int g, const f32x4* b, E (&bd)[2][4]) {
-  typedef E ex4 __attribute__((ext_vector_type(4)));
-  ex4 v[2];
-  const int srow = skew_slot(fr) * RD_PITCH;   // element offset of the lane's scratch row (ATTN_SKEW_RD)
-#pragma unroll
-  for (int pt = 0; pt < 3; ++pt) {
-    const unsigned lo = pack_e2<E>(b[pt][0], b[pt][1]), hi = pack_e2<E>(b[pt][2], b[pt][3]);
-    if constexpr (ATTN_SKEW_RD) {
-      const unsigned waddr = scr_base + 2u * (unsigned)(srow + 16 * pt + 4 * g);
-      asm volatile("ds_write_b64 %0, %1" ::"v"(waddr), "v"((u32x2_a){lo, hi}) : "memory");
-    } else {
-      lds_store_4bf16_a2(scr_base + 2u * (unsigned)(fr * SCR_PITCH + 1 + 16 * pt + 4 * g), lo, hi);
-    }
-  }
-  if constexpr (ATTN_SKEW_RD) {
-    // the 4 values start at a 2-B aligned element: three dwords from the 4-B aligned address at or below it,
-    // funnel-shifted by 0 or 16 bits (tools/probe/skew_probe.hip)
-    u32x2_a d01[2];
-    unsigned d2[2], sh[2];
-#pragma unroll
-    for (int st2 = 0; st2 < 2; ++st2) {
-      const unsigned ra = scr_base + 2u * (unsigned)(srow + 15 - fr + 16 * st2 + 4 * g);
-      const unsigned al = ra & ~3u;
-      sh[st2] = (ra & 2u) << 3;
-      asm volatile("ds_read2_b32 %0, %1 offset0:0 offset1:1" : "=v"(d01[st2]) : "v"(al) : "memory");
-      asm volatile("ds_read_b32 %0, %1 offset:8" : "=v"(d2[st2]) : "v"(al) : "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(d01[0]), "+v"(d01[1]), "+v"(d2[0]), "+v"(d2[1])::"memory");
-#pragma unroll
-    for (int st2 = 0; st2 < 2; ++st2)
-      v[st2] = __builtin_bit_cast(ex4, (u32x2_a){__builtin_amdgcn_alignbit(d01[st2].y, d01[st2].x, sh[st2]),
-                                                 __builtin_amdgcn_alignbit(d2[st2], d01[st2].y, sh[st2])});
-  } else {
-#pragma unroll
-    for (int st2 = 0; st2 < 2; ++st2)
-      asm volatile("ds_read_b64 %0, %1"
-                   : "=v"(v[st2])
-                   : "v"(scr_base + 2u * (unsigned)(fr * (SCR_PITCH - 1) + 16 + 16 * st2 + 4 * g))
-                   : "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0]), "+v"(v[1])::"memory");
-  }
-#pragma unroll
-  for (int st2 = 0; st2 < 2; ++st2)
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) bd[st2][rr] = v[st2][rr];
-}
-// ATTN_SKEW_OVL (ring kernel, ATTN_SKEW_RD): skew_half split in two, so the second half's round trip through
-// the scratch is in flight while the first half's score MFMAs run (the wait names their results, which pins
-// them between the reads' issue and the wait)
-#ifndef ATTN_SKEW_OVL
-#define ATTN_SKEW_OVL 2   // 0: skew_half per half; 1: half 1 in flight under half 0's score MFMAs (ring 4.35 -> 4.26 ms/step); 2: also band subtiles 3-4 under half 0's round trip (4.28 -> 4.22)
-#endif
-#ifndef ATTN_SKEW_PERMC
-#define ATTN_SKEW_PERMC 1   // ring (bf16) and dense kernels: skew_finish_c (v_perm_b32 into the f32 C operand)
-#endif
+// The round trip is split in an issue and a finish, so the second half's trip through the scratch is in flight
+// while the first half's score MFMAs run (the wait names their results, which pins them between the reads'
+// issue and the wait)
 struct SkewRd {
   u32x2_a d01[2];
   unsigned d2[2], sh[2];
@@ -410,18 +328,14 @@ CFM_DEV void skew_finish(const SkewRd& r, E (&bd)[2][4]) {
     for (int rr = 0; rr < 4; ++rr) bd[st2][rr] = v[rr];
   }
 }
-#ifndef ATTN_STAGGER
-#define ATTN_STAGGER 0   // A/B: waves 4-7 store their output rows one pair late (see the ring kernel)
-#endif
-#ifndef ATTN_STORE16
-#define ATTN_STORE16 1   // ring kernel output as 16-B stores after permlane swaps (A/B: 0 = 8-B stores)
-#endif
 
 // DG: the timing / A-B hooks of `diag` are compiled in (the production instantiation has none of their
 // uniform branches inside the tile loop, which would cut it into basic blocks the scheduler cannot
 // interleave across); NTI = W / 64 when W is whole 64-key tiles (1..5), else 0; V4 = next-pair staging in row
-// quads (the launcher: RING_V4 && W % 4 == 0), else in row pairs
-template <bool DG, int NTI, typename E = bf16, bool V4 = (RING_V4 != 0)>
+// quads (8-B V^T stores, half the store instructions; the launcher: W % 4 == 0), else in row pairs: the staged
+// rows start at flat row c0 C + (cp - c0) C + W + C + 4k = W (mod 4), and a quad must not straddle the ring
+// wrap (RING % 4 == 0) nor split an 8-B V^T store
+template <bool DG, int NTI, typename E = bf16, bool V4 = true>
 __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
     const E* __restrict__ Q, const E* __restrict__ KV, int kv_rows, const E* __restrict__ P, int p_rows,
     const float* __restrict__ pos_u, const float* __restrict__ pos_v, const int32_t* __restrict__ desc, int n_chunks,
@@ -523,7 +437,6 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
   }
   // the output rows of a query group: O^T / l as E, dims 16nt + 4g .. of query row op
   auto store_out = [&](const f32x4 (&O)[4], float inv, E* op) {
-  #if ATTN_STORE16
     // dim pairs (16 nt .. +15, 16 (nt+1) ..): one permlane16 swap per packed dword leaves lane g with
     // 8 contiguous dims, so each query row leaves as two 64-B pieces (2 x 16-B stores per lane)
 #pragma unroll
@@ -535,25 +448,8 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
       const auto r1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       *reinterpret_cast<u32x4*>(op + 32 * pr + 16 * (g & 1) + 8 * (g >> 1)) = (u32x4){r0[0], r1[0], r0[1], r1[1]};
     }
-  #else
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      typedef E ex4 __attribute__((ext_vector_type(4)));
-      *reinterpret_cast<ex4*>(op + 16 * nt + 4 * g) =
-          (ex4){(E)(O[nt][0] * inv), (E)(O[nt][1] * inv), (E)(O[nt][2] * inv), (E)(O[nt][3] * inv)};
-    }
-  #endif
   };
-  // ATTN_STAGGER: waves 4-7 keep their finished O across the staging barriers and store it at the start of
-  // the next pair (offsets the SIMD partners' phases by the epilogue; MI355X_MICROARCH.md item 9)
-  f32x4 Od[4];
-  float invd = 0.f;
-  E* opd = nullptr;
   for (int cp = c0; cp < c1; cp += 2) {
-    if (ATTN_STAGGER && opd) {
-      store_out(Od, invd, opd);
-      opd = nullptr;
-    }
     const int kvp = kvb + (cp - c0) * C;
     const int c = cp + half;
     const bool active = c < c1 && i0 < C && (diag & 15) != 1;
@@ -635,9 +531,6 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
         f32x4 S[NTT][4];
         f32x4 band_next = (f32x4){0.f, 0.f, 0.f, 0.f};
         float mx = -INFINITY;
-        // RING_KPF (interior chunks): tile t + 1's K fragments are read right after tile t's band
-        // MFMAs, so their LDS latency overlaps tile t's skew round trip
-        ex8 kf_next[4][2];
         auto load_kf = [&](int t, ex8 (&kf)[4][2]) {
 #pragma unroll
           for (int st = 0; st < 4; ++st) {
@@ -646,8 +539,6 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
             for (int s = 0; s < 2; ++s) kf[st][s] = *reinterpret_cast<const ex8*>(kb_ + frag_lane[s]);
           }
         };
-        constexpr bool KPF = RING_KPF && !MASK;
-        if constexpr (KPF) load_kf(0, kf_next);
 #pragma unroll
         for (int t = 0; t < NTT; ++t) {
           const int j0 = jb + 64 * t;
@@ -670,19 +561,13 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
 #pragma unroll
             for (int s = 0; s < 2; ++s) pf[pt][s] = *reinterpret_cast<const ex8*>(pb_ + frag_lane[s]);
           }
-          if constexpr (KPF) {
-#pragma unroll
-            for (int st = 0; st < 4; ++st) { kf[st][0] = kf_next[st][0]; kf[st][1] = kf_next[st][1]; }
-          } else {
-            load_kf(t, kf);
-          }
+          load_kf(t, kf);
           // band^T[P row kb0 + 16pt + 4g + rr][query fr], pt = 0..4 (80 rows for 64 keys + 15 skew); the
           // two 32-key halves use subtiles 0-2 and 2-4 -> scratch[query][band pos] (16 x 48 E per wave)
           f32x4 band[5];
-          // ATTN_SKEW_OVL 2: subtiles 3-4 (half 1 only) are computed while half 0's round trip is in flight
-          constexpr bool BAND_SPLIT = ATTN_SKEW_OVL >= 2 && ATTN_SKEW_RD;
+          // subtiles 3-4 (half 1 only) are computed while half 0's round trip is in flight
 #pragma unroll
-          for (int pt = 0; pt < (BAND_SPLIT ? 3 : 5); ++pt) {
+          for (int pt = 0; pt < 3; ++pt) {
             if (pt == 0 && carry) {
               band[0] = band_next;
               continue;
@@ -692,72 +577,49 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
             for (int s = 0; s < 2; ++s) a = mma16(pf[pt][s], qv[s], a);
             band[pt] = a;
           }
-          if constexpr (!BAND_SPLIT) band_next = band[4];
-          if constexpr (KPF) {
-            if (t + 1 < NTT) load_kf(t + 1, kf_next);
+          SkewRd r0, r1;
+          skew_issue<E>(scr_base, fr, g, band, r0);
+          asm volatile("" : "+v"(qv[0]), "+v"(qv[1]));   // the MFMAs below read qv after the issue
+#pragma unroll
+          for (int pt = 3; pt < 5; ++pt) {
+            f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 2; ++s) a = mma16(pf[pt][s], qv[s], a);
+            band[pt] = a;
           }
-          if constexpr (ATTN_SKEW_OVL && ATTN_SKEW_RD) {
-            SkewRd r0, r1;
-            skew_issue<E>(scr_base, fr, g, band, r0);
-            if constexpr (BAND_SPLIT) {
-              asm volatile("" : "+v"(qv[0]), "+v"(qv[1]));   // the MFMAs below read qv after the issue
-#pragma unroll
-              for (int pt = 3; pt < 5; ++pt) {
-                f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int s = 0; s < 2; ++s) a = mma16(pf[pt][s], qv[s], a);
-                band[pt] = a;
-              }
-              band_next = band[4];
-              asm volatile("s_waitcnt lgkmcnt(0)"
-                           : "+v"(r0.d01[0]), "+v"(r0.d01[1]), "+v"(r0.d2[0]), "+v"(r0.d2[1]), "+v"(band[3]), "+v"(band[4])::"memory");
+          band_next = band[4];
+          asm volatile("s_waitcnt lgkmcnt(0)"
+                       : "+v"(r0.d01[0]), "+v"(r0.d01[1]), "+v"(r0.d2[0]), "+v"(r0.d2[1]), "+v"(band[3]), "+v"(band[4])::"memory");
+          // the band as the f32 C operand of half hh's score MFMAs
+          auto finish = [&](const SkewRd& r, f32x4 (&c)[2]) {
+            if constexpr (std::is_same<E, bf16>::value) {
+              skew_finish_c(r, c);
             } else {
-              asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r0.d01[0]), "+v"(r0.d01[1]), "+v"(r0.d2[0]), "+v"(r0.d2[1])::"memory");
+              E bdv[2][4];
+              skew_finish<E>(r, bdv);
+#pragma unroll
+              for (int st2 = 0; st2 < 2; ++st2)
+                c[st2] = (f32x4){(float)bdv[st2][0], (float)bdv[st2][1], (float)bdv[st2][2], (float)bdv[st2][3]};
             }
-            // the band as the f32 C operand of half hh's score MFMAs
-            auto finish = [&](const SkewRd& r, f32x4 (&c)[2]) {
-              if constexpr (ATTN_SKEW_PERMC && std::is_same<E, bf16>::value) {
-                skew_finish_c(r, c);
-              } else {
-                E bdv[2][4];
-                skew_finish<E>(r, bdv);
-#pragma unroll
-                for (int st2 = 0; st2 < 2; ++st2)
-                  c[st2] = (f32x4){(float)bdv[st2][0], (float)bdv[st2][1], (float)bdv[st2][2], (float)bdv[st2][3]};
-              }
-            };
-            auto scores = [&](int hh, const f32x4 (&c)[2]) {
-#pragma unroll
-              for (int st2 = 0; st2 < 2; ++st2) {
-                f32x4 a = c[st2];
-#pragma unroll
-                for (int s = 0; s < 2; ++s) a = mma16(kf[2 * hh + st2][s], qu[s], a);
-                S[t][2 * hh + st2] = a;
-              }
-            };
-            f32x4 c0[2], c1[2];
-            finish(r0, c0);
-            skew_issue<E>(scr_base, fr, g, band + 2, r1);   // the half-0 reads are complete: the rows may be reused
-            scores(0, c0);
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(r1.d01[0]), "+v"(r1.d01[1]), "+v"(r1.d2[0]), "+v"(r1.d2[1]), "+v"(S[t][0]), "+v"(S[t][1])::"memory");
-            finish(r1, c1);
-            scores(1, c1);
-          } else
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) {
-            E bdv4[2][4];
-            skew_half<E>(scr_base, fr, g, band + 2 * hh, bdv4);
-            // S^T[key 16st + 4g + rr][query fr] = band + K.(q+u)
+          };
+          // S^T[key 16st + 4g + rr][query fr] = band + K.(q+u)
+          auto scores = [&](int hh, const f32x4 (&c)[2]) {
 #pragma unroll
             for (int st2 = 0; st2 < 2; ++st2) {
-              const int st = 2 * hh + st2;
-              f32x4 a = (f32x4){(float)bdv4[st2][0], (float)bdv4[st2][1], (float)bdv4[st2][2], (float)bdv4[st2][3]};
+              f32x4 a = c[st2];
 #pragma unroll
-              for (int s = 0; s < 2; ++s) a = mma16(kf[st][s], qu[s], a);
-              S[t][st] = a;
+              for (int s = 0; s < 2; ++s) a = mma16(kf[2 * hh + st2][s], qu[s], a);
+              S[t][2 * hh + st2] = a;
             }
-          }
+          };
+          f32x4 c0[2], c1[2];
+          finish(r0, c0);
+          skew_issue<E>(scr_base, fr, g, band + 2, r1);   // the half-0 reads are complete: the rows may be reused
+          scores(0, c0);
+          asm volatile("s_waitcnt lgkmcnt(0)"
+                       : "+v"(r1.d01[0]), "+v"(r1.d01[1]), "+v"(r1.d2[0]), "+v"(r1.d2[1]), "+v"(S[t][0]), "+v"(S[t][1])::"memory");
+          finish(r1, c1);
+          scores(1, c1);
           if constexpr (MASK) {
 #pragma unroll
             for (int st = 0; st < 4; ++st)
@@ -828,14 +690,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
         const bool live = qi < q_valid && l > 0.f;
         const float inv = live ? 1.f / l : 0.f;
         E* op = out + (size_t)(q_row0 + qi) * d + h * 64;
-        if (ATTN_STAGGER && half) {   // waves 4-7: the store leaves after the staging barriers
-#pragma unroll
-          for (int nt = 0; nt < 4; ++nt) Od[nt] = O[nt];
-          invd = inv;
-          opd = op;
-        } else {
-          store_out(O, inv, op);
-        }
+        store_out(O, inv, op);
       };
       if (whole) body(std::false_type{});
       else body(std::true_type{});
@@ -854,22 +709,19 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_ring_kernel(
     }
     if ((diag & 15) != 7) __syncthreads();
   }
-  if (ATTN_STAGGER && opd) store_out(Od, invd, opd);
 }
 
 // returns -1 when the shape is not eligible for the ring kernel
 template <typename E>
 int chunk_attention_masked_ring(const E* q, const E* kv, int kv_rows, const E* P, int p_rows,
                                 const float* pos_u, const float* pos_v, const int32_t* desc, int n_chunks, int H,
-                                int C, int W, E* out, hipStream_t st, int diag, int p_ld, int reuse,
-                                int min_chunks) {
+                                int C, int W, E* out, hipStream_t st, int diag, int p_ld, int min_chunks) {
   if (p_ld <= 0) p_ld = H * 64;
   // W <= 320: a query's scores are 5 tiles of 64 keys held in registers (exact softmax)
   if (C <= 0 || C > 64 || (C % 16) || (W & 1) || W > 320 || W + C > RING || p_rows > RING || n_chunks <= 0) return -1;
   // one block per CU (LDS-bound), each sweeping a long run of chunks of one head: one prologue
   // (P rows + first window) per block instead of one per 8 chunks
   const int n_cu = cu_count();
-  if (!reuse && (diag & 15) == 0) diag |= 5;   // "attn_reuse" 0: recompute the shared band subtile (A/B)
   // one block per CU (CUs / H runs per head), each a balanced run of >= 2 chunks: a small launch (an
   // endless_decode segment at tbd 1800: 199 chunks) still fills every CU (was: runs of >= NCH chunks,
   // rounded to pairs -- 200 blocks on 256 CUs there)
@@ -877,7 +729,7 @@ int chunk_attention_masked_ring(const E* q, const E* kv, int kv_rows, const E* P
   const int nch = (n_chunks + gx - 1) / gx;
   const dim3 grid(gx, H);
 #define RING_L(DG_, NT_)                                                                                             \
-  hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, NT_, E, RING_V4 != 0>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, pos_u, \
+  hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, NT_, E, true>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, pos_u, \
                      pos_v, desc, n_chunks, H, C, W, out, diag, nch, p_ld)
 #define RING_P(DG_)                                                                                                   \
   hipLaunchKernelGGL((chunk_attention_ring_kernel<DG_, 0, E, false>), grid, dim3(512), 0, st, q, kv, kv_rows, P, p_rows, \
@@ -904,17 +756,15 @@ int chunk_attention_masked_ring(const E* q, const E* kv, int kv_rows, const E* P
 }
 int chunk_attention_masked_bf16(const bf16* q, const bf16* kv, int kv_rows, const bf16* P, int p_rows,
                                 const float* pos_u, const float* pos_v, const int32_t* desc, int n_chunks, int H,
-                                int C, int W, bf16* out, hipStream_t st, int diag, int p_ld, int reuse,
-                                int min_chunks) {
+                                int C, int W, bf16* out, hipStream_t st, int diag, int p_ld, int min_chunks) {
   return chunk_attention_masked_ring<bf16>(q, kv, kv_rows, P, p_rows, pos_u, pos_v, desc, n_chunks, H, C, W, out, st,
-                                           diag, p_ld, reuse, min_chunks);
+                                           diag, p_ld, min_chunks);
 }
 int chunk_attention_masked_f16(const f16* q, const f16* kv, int kv_rows, const f16* P, int p_rows,
                                const float* pos_u, const float* pos_v, const int32_t* desc, int n_chunks, int H,
-                               int C, int W, f16* out, hipStream_t st, int diag, int p_ld, int reuse,
-                               int min_chunks) {
+                               int C, int W, f16* out, hipStream_t st, int diag, int p_ld, int min_chunks) {
   return chunk_attention_masked_ring<f16>(q, kv, kv_rows, P, p_rows, pos_u, pos_v, desc, n_chunks, H, C, W, out, st,
-                                          diag, p_ld, reuse, min_chunks);
+                                          diag, p_ld, min_chunks);
 }
 
 
@@ -929,7 +779,7 @@ int chunk_attention_masked_f16(const f16* q, const f16* kv, int kv_rows, const f
 // one HBM-bound prologue of 160 KB) per pair; per pass:
 //   K rows (swizzled) from the registers into the K / V^T region;
 //   scores:  the ring kernel's compute -- S^T = K.(q+u)^T, band^T = P.(q+v)^T skewed through a bf16
-//            scratch (skew_half), exact softmax with all <= 384 scores of a query in registers;
+//            scratch (skew_issue / skew_finish_c), exact softmax with all <= 384 scores of a query in registers;
 //   V^T from the registers over the dead K region, then O^T = V^T.P^T with the score registers as
 //            the B operand.
 // LDS: max(K 48 KiB, V^T 49 KiB) + P 96 KiB + 8 skew scratches = 159 KiB.
@@ -1102,18 +952,10 @@ __global__ __launch_bounds__(512, 1) void full_attention_bf16_kernel(
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           f32x4 c[2];
-          if constexpr (ATTN_SKEW_PERMC && ATTN_SKEW_RD) {   // the band straight into the C operand (v_perm_b32)
-            SkewRd r;
-            skew_issue<bf16>(scr_base, fr, g, band + 2 * hh, r);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r.d01[0]), "+v"(r.d01[1]), "+v"(r.d2[0]), "+v"(r.d2[1])::"memory");
-            skew_finish_c(r, c);
-          } else {
-            bf16 bdv4[2][4];
-            skew_half<bf16>(scr_base, fr, g, band + 2 * hh, bdv4);
-#pragma unroll
-            for (int st2 = 0; st2 < 2; ++st2)
-              c[st2] = (f32x4){(float)bdv4[st2][0], (float)bdv4[st2][1], (float)bdv4[st2][2], (float)bdv4[st2][3]};
-          }
+          SkewRd r;   // the band straight into the C operand (v_perm_b32)
+          skew_issue<bf16>(scr_base, fr, g, band + 2 * hh, r);
+          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r.d01[0]), "+v"(r.d01[1]), "+v"(r.d2[0]), "+v"(r.d2[1])::"memory");
+          skew_finish_c(r, c);
 #pragma unroll
           for (int st2 = 0; st2 < 2; ++st2) {
             bf16x8 kf[2];
@@ -1182,7 +1024,6 @@ __global__ __launch_bounds__(512, 1) void full_attention_bf16_kernel(
     const bool live = qi < q_valid && l > 0.f;
     const float inv = live ? 1.f / l : 0.f;
     bf16* op = out + ((size_t)q_row0 + qi) * d + h * 64;
-#if ATTN_STORE16
     // as the ring kernel: 16-B stores after permlane16 swaps (every lane takes part in the swaps)
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
@@ -1193,15 +1034,6 @@ __global__ __launch_bounds__(512, 1) void full_attention_bf16_kernel(
       const auto r1 = __builtin_amdgcn_permlane16_swap(x1, y1, false, false);
       if (qi < nq) *reinterpret_cast<u32x4*>(op + 32 * pr + 16 * (g & 1) + 8 * (g >> 1)) = (u32x4){r0[0], r1[0], r0[1], r1[1]};
     }
-#else
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-      if (qi < nq)
-        *reinterpret_cast<bf16x4*>(op + 16 * nt + 4 * g) =
-            (bf16x4){(bf16)(O[nt][0] * inv), (bf16)(O[nt][1] * inv), (bf16)(O[nt][2] * inv), (bf16)(O[nt][3] * inv)};
-    }
-#endif
     }   // active
     __syncthreads();   // every wave is past its V^T reads before the next pass writes K there
     }   // passes

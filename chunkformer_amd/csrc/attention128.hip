@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void vt_transpose_kernel(const bf16* __restric
 }
 
 // NT = W / 64 key tiles per window (W = L + C + R; 5 at C = 64, L = R = 128)
-template <int NT, int VAR>
+template <int NT>
 __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ KV, int kv_rows, const bf16* __restrict__ VT, int vt_ld,
     const bf16* __restrict__ P, int p_rows, int p_ld, const float* __restrict__ pos_u, const float* __restrict__ pos_v,
@@ -151,10 +151,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
   auto load_vt = [&](int c) {
     const bf16* vp = VT + ((size_t)h * 128 + 16 * w + fr) * vt_ld + (size_t)(kvb + (c - c0) * 64) + 8 * g;
 #pragma unroll
-    for (int ks = 0; ks < 2 * NT; ++ks) {
-      if constexpr (VAR == 13) vf[ks] = (bf16x8){};   // timing only: no V^T loads
-      else vf[ks] = *reinterpret_cast<const bf16x8*>(vp + 32 * ks);
-    }
+    for (int ks = 0; ks < 2 * NT; ++ks) vf[ks] = *reinterpret_cast<const bf16x8*>(vp + 32 * ks);
   };
   __syncthreads();
 
@@ -182,18 +179,13 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
 #pragma unroll
       for (int rs = 0; rs < 3; ++rs) {
         f32x4 a = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if constexpr (VAR != 10) {
 #pragma unroll
-          for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[rs][s], qvf[s], a, 0, 0, 0);
-        }
+        for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf[rs][s], qvf[s], a, 0, 0, 0);
         const int i = 16 * qs + fr;
         const int col = 48 * w + 16 * rs + 4 * g + i - 59;
         if (col >= 1 && col <= W + 3) {   // groups that reach a read column j + 4, j in [0, W)
           const unsigned addr = bb_lds + 2u * (unsigned)(i * A8_BAND_PITCH + col);   // 2-B aligned
-          if constexpr (VAR == 3)   // A/B: one unaligned ds_write_b64 (replayed by the LDS)
-            asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"((u32x2_){pk2(a[0], a[1]), pk2(a[2], a[3])}) : "memory");
-          else
-            lds_store_4bf16_a2(addr, pk2(a[0], a[1]), pk2(a[2], a[3]));
+          lds_store_4bf16_a2(addr, pk2(a[0], a[1]), pk2(a[2], a[3]));
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -210,8 +202,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
     f32x4 S[NSUB];
     float mx = -INFINITY;
     // subtiles in pairs: two independent MFMA chains interleaved, the pair's fragments loaded together
-    // (VAR 0: one subtile at a time)
-    constexpr int PAIR = VAR == 0 ? 1 : 2;
+    constexpr int PAIR = 2;
 #pragma unroll
     for (int t0 = 0; t0 < NSUB; t0 += PAIR) {
       bf16x8 kf[PAIR][4];
@@ -226,12 +217,10 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
         for (int s = 0; s < 4; ++s) kf[u][s] = *reinterpret_cast<const bf16x8*>(kr + sw256(slot + fr, 4 * s + g));
         a[u] = (f32x4){(float)bv[0], (float)bv[1], (float)bv[2], (float)bv[3]};
       }
-      if constexpr (VAR != 11) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+      for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int u = 0; u < PAIR; ++u) a[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[u][s], quf[s], a[u], 0, 0, 0);
-      }
+        for (int u = 0; u < PAIR; ++u) a[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[u][s], quf[s], a[u], 0, 0, 0);
 #pragma unroll
       for (int u = 0; u < PAIR; ++u) S[t0 + u] = a[u] * scale;
       __builtin_amdgcn_sched_barrier(0);   // keep each group's fragment loads next to its MFMAs
@@ -294,8 +283,7 @@ __global__ __launch_bounds__(512, 1) void chunk_attention_a128_kernel(
 #pragma unroll
       for (int qs = 0; qs < 4; ++qs) {
         const bf16x8 pb = *reinterpret_cast<const bf16x8*>(bb + ((16 * qs + fr) * A8_PROB_PITCH + 32 * ks + 8 * g) * 2);
-        if constexpr (VAR != 12) O[qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[ks], pb, O[qs], 0, 0, 0);
-        else O[qs][0] += (float)pb[0];
+        O[qs] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[ks], pb, O[qs], 0, 0, 0);
       }
     }
 #pragma unroll
@@ -325,33 +313,22 @@ bool attention_a128_eligible(int C, int W, int p_rows, int dk) {
 
 int chunk_attention_masked_a128(const bf16* q, const bf16* kv, int kv_rows, const bf16* vt, int vt_ld, const bf16* P,
                                 int p_rows, int p_ld, const float* pos_u, const float* pos_v, const int32_t* desc,
-                                int n_chunks, int H, int C, int W, bf16* out, hipStream_t st, int var) {
+                                int n_chunks, int H, int C, int W, bf16* out, hipStream_t st) {
   if (!attention_a128_eligible(C, W, p_rows, 128) || n_chunks <= 0) return -1;
   const int n_cu = cu_count();
   // one block per CU sweeping consecutive chunks of one head (one K-ring prologue per block)
   int nch = (int)(((long long)n_chunks * H + n_cu - 1) / n_cu);
   nch = std::max(4, nch);
   const dim3 grid((n_chunks + nch - 1) / nch, H);
-#define A128(NT_, V_)                                                                                                \
-  hipLaunchKernelGGL((chunk_attention_a128_kernel<NT_, V_>), grid, dim3(512), 0, st, q, kv, kv_rows, vt, vt_ld, P,   \
-                     p_rows, p_ld, pos_u, pos_v, desc, n_chunks, H, nch, out)
-  // var ("attn128_var" model option, A/B): 1 = paired score subtiles (default), 0 = one at a time
+#define A128(NT_)                                                                                                    \
+  hipLaunchKernelGGL((chunk_attention_a128_kernel<NT_>), grid, dim3(512), 0, st, q, kv, kv_rows, vt, vt_ld, P, p_rows, \
+                     p_ld, pos_u, pos_v, desc, n_chunks, H, nch, out)
   switch (W / 64) {
-    case 1: A128(1, 1); break;
-    case 2: A128(2, 1); break;
-    case 3: A128(3, 1); break;
-    case 4: A128(4, 1); break;
-    default:
-      switch (var) {   // 10-13: timing-only diagnostics (no band / score / P.V MFMAs, no V^T loads)
-        case 0: A128(5, 0); break;
-        case 3: A128(5, 3); break;
-        case 10: A128(5, 10); break;
-        case 11: A128(5, 11); break;
-        case 12: A128(5, 12); break;
-        case 13: A128(5, 13); break;
-        default: A128(5, 1); break;
-      }
-      break;
+    case 1: A128(1); break;
+    case 2: A128(2); break;
+    case 3: A128(3); break;
+    case 4: A128(4); break;
+    default: A128(5); break;
   }
 #undef A128
   CFM_CHECK_LAUNCH();

@@ -57,9 +57,6 @@ enum { SITE_QKV = 1, SITE_OPROJ = 2, SITE_PW2 = 4, SITE_FFN2 = 8, SITE_FFN1 = 16
 // Per-model kernel tuning (cfm_model_set_option); the defaults are the measured best
 struct Tuning {
   int gemm_diag = 0, gemm_wst = 1, store_mode = 0, col_group = 0;
-  int attn_reuse = 1;            // ring attention: band subtile carried between key tiles
-  int conv_dot2 = 2;             // conv module: bf16 dot2 kernel in half-chunk blocks (1: one block per chunk, 0: per-tap f32)
-  int conv_dma = 1;              // conv module: LDS-DMA window staging (0: register staging)
   int dw2_seg = 4;               // front-end dw2: row segments per walk
   int fe_conv = 6;               // bf16 front-end conv0+dw1: 1 = position-stationary (dw1 on VALU), 2 + k = channel-
                                  // stationary with dw1 on MFMA, ~k + 1 chunks per workgroup (2.74 vs 3.10 ms/step);
@@ -67,7 +64,6 @@ struct Tuning {
                                  // are created with 1 (build_model)
   int fe_fuse_dw2 = 1;           // front-end: pw1 + ReLU + dw2 in one weight-stationary GEMM (bf16; bench A/B
                                  // 50.85 -> 50.15 ms/step, 3 interleaved pairs; 0 = pw1 GEMM + fe_dw2_kernel)
-  int attn128_var = 1;           // head_dim 128 attention kernel variant (A/B)
   // GEMM sites whose bf16 outputs are stored non-temporally ("nt_sites" bit mask, SITE_* below).
   // Default: FFN w2 (its y goes straight to the LayerNorm; bench A/B 52.2 -> 51.4 ms/step); nt on
   // the front-end pointwise outputs (+0.45 ms) or FFN w1's hidden (w1 slower) measured worse.
@@ -134,12 +130,12 @@ int full_attention_bf16(const bf16* q, const bf16* kv, int kv_rows, const bf16* 
                         bf16* out, hipStream_t st, int p_ld);
 int chunk_attention_masked_bf16(const bf16* q, const bf16* kv, int kv_rows, const bf16* P, int p_rows,
                                 const float* pos_u, const float* pos_v, const int32_t* desc, int n_chunks, int H,
-                                int C, int W, bf16* out, hipStream_t st, int diag = 0, int p_ld = 0, int reuse = 1,
+                                int C, int W, bf16* out, hipStream_t st, int diag = 0, int p_ld = 0,
                                 int min_chunks = 2);
 // the same ring kernel on f16 operands (v_mfma_f32_16x16x32_f16; the fp16 compute mode)
 int chunk_attention_masked_f16(const f16* q, const f16* kv, int kv_rows, const f16* P, int p_rows,
                                const float* pos_u, const float* pos_v, const int32_t* desc, int n_chunks, int H,
-                               int C, int W, f16* out, hipStream_t st, int diag = 0, int p_ld = 0, int reuse = 1,
+                               int C, int W, f16* out, hipStream_t st, int diag = 0, int p_ld = 0,
                                int min_chunks = 2);
 
 // masked-batch attention for head_dim 128 (attention128.hip): V^T copy of the KV stream, then the
@@ -148,13 +144,12 @@ bool attention_a128_eligible(int C, int W, int p_rows, int dk);
 int vt_transpose_bf16(const bf16* kv, int kv_rows, int H, bf16* vt, int vt_ld, hipStream_t st);
 int chunk_attention_masked_a128(const bf16* q, const bf16* kv, int kv_rows, const bf16* vt, int vt_ld, const bf16* P,
                                 int p_rows, int p_ld, const float* pos_u, const float* pos_v, const int32_t* desc,
-                                int n_chunks, int H, int C, int W, bf16* out, hipStream_t st, int var = 1);
+                                int n_chunks, int H, int C, int W, bf16* out, hipStream_t st);
 
 // conv module: depthwise k=15 + bias + LayerNorm + SiLU (conv_module.hip)
 template <typename T>
 int conv_dw_ln_silu(const T* glu, const int32_t* desc, int nblk, int d, const float* wdw_t /*[15][d]*/,
-                    const float* bdw, const float* lnw, const float* lnb, float eps, T* out, hipStream_t st,
-                    int dot2 = 1, int dma = 1);
+                    const float* bdw, const float* lnw, const float* lnb, float eps, T* out, hipStream_t st);
 
 // front-end (frontend.hip): meta rows give (src_row, nvalid) per window at PM_SRC_ROW / PM_NVALID;
 // with `tab` (device array of per-utterance row pointers) window c of utterance u starts at

@@ -268,19 +268,8 @@ __global__ __launch_bounds__(256, 3) void fe_conv0_dw_mfma_kernel(const float* _
 // tap 8 + 1.0 + zeros in the "hi" image, 16 B each, even and odd conv0 columns in separate planes so
 // the 32 lanes of a tap read consecutive 16-B slots), so a tap's B fragment is one ds_read_b128 at a
 // constant offset.  The next chunk's input rows are loaded into registers while this chunk computes.
-#ifndef FE2_POS_DEF
-#define FE2_POS_DEF 256
-#endif
-#ifndef FE2_WAVES
-#define FE2_WAVES 4   // waves (32-channel tiles) per workgroup sharing one im2col build: 4 (2 workgroups per CU) or 8
-#endif
-#ifndef FE2_PRIO
-#define FE2_PRIO 0
-#endif
-#ifndef FE2_STG
-#define FE2_STG 1   // output staging buffers per wave (2: a tile's outputs leave during the next tile; 2.709 vs 2.688 ms)
-#endif
-constexpr int FE2_POS = FE2_POS_DEF;                                  // dw1 positions per chunk
+constexpr int FE2_WAVES = 4;   // waves (32-channel tiles) per workgroup sharing one im2col build (2 workgroups per CU)
+constexpr int FE2_POS = 256;                                          // dw1 positions per chunk
 constexpr int FE2_T1ROWS = 2 * ((FE_F2 - 1 + FE2_POS - 1) / FE_F2) + 3;   // conv0 rows a chunk can touch
 constexpr int FE2_XROWS = 2 * FE2_T1ROWS + 1;                         // input rows behind them
 constexpr int FE2_SLOTS = (FE_F1 + 1) / 2;                            // conv0 columns per parity plane
@@ -296,11 +285,7 @@ constexpr int FE2_NT = 64 * FE2_WAVES;                                // threads
 constexpr int FE2_QPT = (FE2_NQ + FE2_NT - 1) / FE2_NT;               // ... per thread
 typedef short short2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef bf16 bf16x2v __attribute__((ext_vector_type(2)));
 
-#ifndef FE2_CLAMP
-#define FE2_CLAMP 1   // ReLU as the clamp modifier of the conversion (see fe2_relu_pk); 0: v_pk_max_i16
-#endif
 template <typename E>
 __device__ __forceinline__ unsigned fe2_relu_pk(float a, float b) {
   if constexpr (std::is_same<E, f16>::value) {   // f16: RNE pack, then the ReLU as a packed int16 max
@@ -309,8 +294,7 @@ __device__ __forceinline__ unsigned fe2_relu_pk(float a, float b) {
     v = __builtin_elementwise_max(v, (short2v){0, 0});
     return __builtin_bit_cast(unsigned, v);
   }
-#if FE2_CLAMP
-  // W0 and b0 enter the fragments scaled by 2^-24 and w1 by 2^24 (exact: powers of two), so conv0's
+  // bf16: the ReLU as the clamp modifier of the conversion.  W0 and b0 enter the fragments scaled by 2^-24 and w1 by 2^24 (exact: powers of two), so conv0's
   // accumulator is the true value times 2^-24 and, for |conv0| < 2^24, the conversion's clamp to
   // [0, 1] is exactly the ReLU: one instruction per pair instead of two (saturation to [0, 1], NaN to 0,
   // probed on gfx950: tools/probe/cvt_clamp.hip).  Front-end conv0 outputs of CMVN-normalised
@@ -318,11 +302,6 @@ __device__ __forceinline__ unsigned fe2_relu_pk(float a, float b) {
   unsigned u;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2 clamp" : "=v"(u) : "v"(a), "v"(b));
   return u;
-#endif
-  const bf16x2v pr = __builtin_convertvector((f32x2v){a, b}, bf16x2v);   // one v_cvt_pk_bf16_f32
-  short2v v = __builtin_bit_cast(short2v, pr);
-  v = __builtin_elementwise_max(v, (short2v){0, 0});   // v_pk_max_i16: a negative bf16 is a negative int16
-  return __builtin_bit_cast(unsigned, v);
 }
 
 // 8 f32 -> the 16-bit format (RNE), as a bf16x8 container of raw lanes
@@ -340,7 +319,7 @@ __device__ __forceinline__ f32x16 fe2_mfma(const bf16x8& a, const bf16x8& b, con
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 template <typename E>
-__global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kernel(const float* __restrict__ feats,
+__global__ __launch_bounds__(FE2_NT, 2) void fe_conv0_dw_mfma2_kernel(const float* __restrict__ feats,
                                                                 const float* const* __restrict__ tab, int step,
                                                                 const int32_t* __restrict__ meta, int meta_stride,
                                                                 int W, int T2, const float* __restrict__ cm,
@@ -349,7 +328,7 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
                                                                 E* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) char im2col[2 * FE2_IMG];
   // the chunk's input rows (f32, CMVN applied) while im2col is built; then the waves' output staging
-  constexpr int XBYTES = FE2_XROWS * FE_F0 * 4, OBYTES = FE2_STG * FE2_WAVES * 32 * FE2_OPITCH;   // output staging
+  constexpr int XBYTES = FE2_XROWS * FE_F0 * 4, OBYTES = FE2_WAVES * 32 * FE2_OPITCH;   // output staging
   __shared__ __attribute__((aligned(16))) char xstage[XBYTES > OBYTES ? XBYTES : OBYTES];
   __shared__ __attribute__((aligned(16))) float cmvn[2][FE_F0];
   const int tid = threadIdx.x;
@@ -358,11 +337,6 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
   const int win = blockIdx.z;
   const int P = T2 * FE_F2;
   const int ct = blockIdx.y * FE2_WAVES + wv;   // this wave's 32-channel tile (waves past d only help build)
-  // FE2_PRIO (A/B): static priority for one of a SIMD's two partner waves (MI355X_MICROARCH.md, two waves per
-  // SIMD, item 4): waves 4-7 of an 8-wave workgroup, or the odd channel groups' workgroups
-  if constexpr (FE2_PRIO) {
-    if (FE2_WAVES == 8 ? wv >= 4 : (blockIdx.y & 1) != 0) __builtin_amdgcn_s_setprio(1);
-  }
   const bool active = ct * 32 < d;
   // loop-invariant operands (host-built per-lane fragments, model.hip), loaded first so their latency
   // overlaps the first chunk's input loads: W0 rows (+ b0 at k = 9), the diagonal dw1 fragments, the
@@ -405,7 +379,7 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
                                  (unsigned)__builtin_amdgcn_readfirstlane((unsigned)obase);
   const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
       (void*)obu, (short)0, __builtin_amdgcn_readfirstlane(P * d * 2), 0x00020000);
-  char* os = xstage + wv * 32 * FE2_OPITCH;   // this wave's staging; its second buffer FE2_WAVES waves further on
+  char* sb = xstage + wv * 32 * FE2_OPITCH;   // this wave's output staging
   const f32x16 zero = {};
   for (int c = c_beg; c < c_end; ++c) {
     const int p0 = c * FE2_POS, t2a = p0 / FE_F2;
@@ -483,13 +457,11 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
 #pragma unroll
       for (int s = 0; s < 9; ++s) pb[s] = ld(xb, s);
     }
-    int it = 0;
-    for (int pt = p0; pt < pend; pt += 32, ++it) {
+    for (int pt = p0; pt < pend; pt += 32) {
       // the next tile's patches are read into pb as its registers free up (tap t's patch is last
       // used when conv0 of tap t is issued, in loop step t - 1), so they arrive under this tile's
-      // MFMAs; the previous tile's staged outputs leave in step 1
+      // MFMAs
       const char* xbn = patch_base(pt + 32 < pend ? pt + 32 : pt);
-      char* sb = os + (FE2_STG == 2 ? (it & 1) : 0) * (FE2_WAVES * 32 * FE2_OPITCH);
       f32x16 y = seed;
       f32x16 acc = fe2_mfma<E>(a0, pb[0], zero);
 #pragma unroll
@@ -505,7 +477,6 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
         }
         y = fe2_mfma<E>(a1[s][0], __builtin_bit_cast(bf16x8, r0), y);
         y = fe2_mfma<E>(a1[s][1], __builtin_bit_cast(bf16x8, r1), y);
-        if (FE2_STG == 2 && s == 1 && it > 0) flush(os + ((it - 1) & 1) * (FE2_WAVES * 32 * FE2_OPITCH), pt - 32);
         if (s == 3) {
 #pragma unroll
           for (int t = 0; t < 4; ++t) pb[t] = ld(xbn, t);
@@ -528,10 +499,8 @@ __global__ __launch_bounds__(FE2_NT, 8 / FE2_WAVES) void fe_conv0_dw_mfma2_kerne
                                      ((unsigned long long)__builtin_bit_cast(unsigned, hi) << 32);
         *reinterpret_cast<unsigned long long*>(sb + n * FE2_OPITCH + (8 * g + 4 * h) * 2) = u;
       }
-      if (FE2_STG == 1) flush(sb, pt);
+      flush(sb, pt);
     }
-    if (FE2_STG == 2 && it > 0)
-      flush(os + ((it - 1) & 1) * (FE2_WAVES * 32 * FE2_OPITCH), pend - 1 - ((pend - 1 - p0) % 32));
   }
 }
 

@@ -39,12 +39,8 @@ constexpr int WST_KS = 64;              // K per step
 constexpr int WST_NK = WST_K / WST_KS;  // 8 steps per tile
 constexpr int WST_SLOT = WST_MT * WST_KS * 2;   // 8 KiB
 constexpr int WST_NSLOT = 16;
-#ifndef WSP_BARP
-#define WSP_BARP 2   // K-steps per barrier (1, 2 or 4): the DMA runs 16 - WSP_BARP steps ahead and refills
-                     // the slot of step y - WSP_BARP, so only every WSP_BARP-th step needs the barrier
-#endif
-constexpr int WST_DEPTH = WST_NSLOT - WSP_BARP;   // steps in flight ahead of the one being read
-static_assert(WSP_BARP == 1 || WSP_BARP == 2 || WSP_BARP == 4, "barrier period");
+constexpr int WSP_BARP = 2;   // K-steps per barrier: the DMA runs 16 - WSP_BARP steps ahead and refills
+                              // the slot of step y - WSP_BARP, so only every WSP_BARP-th step needs the barrier
 // DW2 (front-end pw1 + ReLU + dw2): an 8-slot A ring leaves LDS for the pw1 output ring
 template <int EPI> constexpr int wst_nslot() { return EPI == EPI_DW2 ? 8 : WST_NSLOT; }
 #ifndef DW2_BARP
@@ -102,15 +98,6 @@ template <int FMT> CFM_DEV f32x2 dw2_unpk2(unsigned x) {
 }
 }  // namespace
 
-#ifndef WSP_LGKM
-#define WSP_LGKM 1   // 0: every K-step closes with lgkmcnt(0) (re-seed reads waited at once)
-#endif
-#ifndef WSP_FULLROW
-#define WSP_FULLROW 1   // 0: permlane-swapped 64-B row pieces stored per step (A/B)
-#endif
-#ifndef WSP_FULLROW_ACT
-#define WSP_FULLROW_ACT 1   // also the SiLU / ReLU epilogues (0: permlane-swapped 64-B pieces there; A/B)
-#endif
 #define WST_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
 
 // acc += W-fragment (AGPR, "a") x A-fragment (VGPR): the 256 weight registers per lane live in the
@@ -153,7 +140,7 @@ CFM_DEV void lds_read_into(bf16x8& v, unsigned addr) {
 
 namespace {
 // micro-ops of epilogue group s (0..7).  STORE/QKV: two halves (one 16-column n-block each) of
-// [activation ops on 4 values, 2 packs], then 2 permlane swaps, 1 store, 2 re-seeds.
+// [activation ops on 4 values, 2 packs], the staging-tile write and read-back, 2 re-seeds (full rows, below).
 // GLU: group s = (m-block s/2, channel half s%1): 20 sigmoid-gate ops + 2 packs (+ swaps and the
 // store on odd s), 2 re-seeds.
 template <int ACT>
@@ -162,7 +149,7 @@ constexpr int wsp_half() { return (ACT == ACT_SILU ? 20 : ACT == ACT_SILU_L2E ? 
 // 2 packs, 2 re-seeds, 2 swaps and (odd groups) the store
 template <int ACT>
 constexpr int glu_chain() { return ACT == ACT_SILU_L2E ? 16 : 20; }
-// Full-row stores (non-GLU, WSP_FULLROW): per half q the activation ops, 2 packs, one ds_write_b64
+// Full-row stores (STORE / QKV): per half q the activation ops, 2 packs, one ds_write_b64
 // of the 4 packed columns into the wave's 16 x 64 staging tile, the re-seed; an odd group then
 // reads the tile back as full 128-B rows (2 x ds_read_b128: rows 0-7, 8-15) and the next (even)
 // group stores them first thing (its step opened with lgkmcnt(0)).  2H + 4 ops either way.
@@ -170,16 +157,14 @@ constexpr int glu_chain() { return ACT == ACT_SILU_L2E ? 16 : 20; }
 // On random-data microbenchmarks (power-limited clocks) the SiLU / ReLU epilogues measured 2-6% slower
 // with it, but in the bench step (real activations, 2.3 GHz) FFN w1 9.1 -> 8.3 ms/step and the
 // front-end pointwise GEMMs 5.2 -> 4.8 ms/step (3 interleaved runs each), so it is on there too.
-template <int EPI, int ACT>
-constexpr bool wsp_fullrow() {
-  return WSP_FULLROW && (EPI == EPI_QKV || (EPI == EPI_STORE && (ACT == ACT_NONE || WSP_FULLROW_ACT)));
-}
+template <int EPI>
+constexpr bool wsp_fullrow() { return EPI == EPI_QKV || EPI == EPI_STORE; }
 // DW2 groups: per half q the activation ops, 2 packs, the ds_write_b64 into the pw1 ring, the re-seed
 template <int EPI, int ACT>
 constexpr int wsp_nops(int s) {
   return EPI == EPI_DW2 ? 2 * (wsp_half<ACT>() + 2)
          : EPI == EPI_GLU ? glu_chain<ACT>() + ((s & 1) ? 7 : 4)
-         : wsp_fullrow<EPI, ACT>() ? 2 * wsp_half<ACT>() + 6 : 2 * wsp_half<ACT>() + 5;
+         : 2 * wsp_half<ACT>() + 6;
 }
 constexpr int wsp_lo(int i, int n) { return (i * n + 31) / 32; }   // first op of gap i
 constexpr int wsp_gap(int o, int n) {                                  // gap that carries op o
@@ -195,10 +180,9 @@ constexpr int wsp_late_seeds(int s) {
   const int n = wsp_nops<EPI, ACT>(s), H = wsp_half<ACT>() + 1;
   // full-row: even groups open with the 2 deferred stores (seeds at 2 + H, 2H + 3); odd groups
   // end with the 2 row reads and then both seeds (2H + 2, 2H + 3)
-  const bool fr = wsp_fullrow<EPI, ACT>();
   const int G = glu_chain<ACT>();
-  const int o0 = EPI == EPI_DW2 ? H : EPI == EPI_GLU ? G + 2 : fr ? ((s & 1) ? 2 * H + 2 : H + 2) : H - 1;
-  const int o1 = EPI == EPI_DW2 ? 2 * H + 1 : EPI == EPI_GLU ? G + 3 : fr ? 2 * H + 3 : 2 * H - 1;
+  const int o0 = EPI == EPI_DW2 ? H : EPI == EPI_GLU ? G + 2 : (s & 1) ? 2 * H + 2 : H + 2;
+  const int o1 = EPI == EPI_DW2 ? 2 * H + 1 : EPI == EPI_GLU ? G + 3 : 2 * H + 3;
   return (wsp_gap(o0, n) >= 14) + (wsp_gap(o1, n) >= 14);
 }
 }  // namespace
@@ -470,35 +454,6 @@ __global__ __launch_bounds__(256, 1) void gemm_wsp_kernel(const bf16* __restrict
       } else {   // O == G + 6
         store(0, jj);
       }
-    } else if constexpr (!wsp_fullrow<EPI, ACT>()) {
-      // ops: per half q (one 16-column n-block) H - 2 activation ops, 2 packs and the re-seed of
-      // that n-block's accumulator (dead after the packs), then 2 swaps and the store
-      constexpr int p = S & 1, jj = S >> 1;   // the two 64-B halves of a 128-B row piece in consecutive steps
-      constexpr int H = wsp_half<ACT>() + 1;
-      if constexpr (O < 2 * H && O % H == H - 1) {
-        seed(std::integral_constant<int, 2 * p + O / H>{}, jj);
-      } else if constexpr (DIAG == 3) {
-      } else if constexpr (O < 2 * H) {
-        constexpr int q = O / H, o = O % H;
-        auto val = [&](int i) -> float { return a[2 * p + q][jj][i]; };
-        if constexpr (o < H - 3) {
-          if constexpr (ACT == ACT_SILU || ACT == ACT_SILU_L2E) {
-            chain(o, val, val);
-          } else {
-            et[o] = fmaxf(val(o), 0.f);
-            pin(et[o]);
-          }
-        } else {
-          constexpr int k = o - (H - 3);   // pack k of this half: values 2k, 2k+1
-          if constexpr (ACT == ACT_NONE) epk[2 * q + k] = pack_h2<FMT>(val(2 * k), val(2 * k + 1));
-          else epk[2 * q + k] = pack_h2<FMT>(et[2 * k], et[2 * k + 1]);
-          pin(epk[2 * q + k]);
-        }
-      } else if constexpr (O < 2 * H + 2) {
-        swap(O - 2 * H);
-      } else {   // O == 2H + 2
-        store(p, jj);
-      }
     } else {
       // full rows.  even S: the 2 stores of the previous (odd) group's rows, then per half q
       // (n-block 2p + q) the activation ops, 2 packs, the ds_write_b64 into the staging tile and
@@ -589,7 +544,7 @@ __global__ __launch_bounds__(256, 1) void gemm_wsp_kernel(const bf16* __restrict
         __builtin_amdgcn_sched_barrier(0);
       });
       constexpr int late = wsp_late_seeds<EPI, ACT>(KS);
-      if constexpr (KS == WST_NK - 1 || late == 0 || !WSP_LGKM)
+      if constexpr (KS == WST_NK - 1 || late == 0)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       else if constexpr (late == 1)
         asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");
@@ -608,7 +563,7 @@ __global__ __launch_bounds__(256, 1) void gemm_wsp_kernel(const bf16* __restrict
   };
   // the full-row path's last pending rows (group 7 of the last drained tile, descriptor sd)
   auto flush_rows = [&](const StoreD& sd) {
-    if constexpr (wsp_fullrow<EPI, ACT>() && DIAG != 5) {
+    if constexpr (wsp_fullrow<EPI>() && DIAG != 5) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
       for (int b = 0; b < 2; ++b)

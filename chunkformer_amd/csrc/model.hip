@@ -185,10 +185,7 @@ namespace cfm {
 
 // 16-bit modes run the FFN SiLU and the conv module's GLU on -log2(e)-prescaled accumulators (ACT_SILU_L2E,
 // cfm_kernels.h): the weights are scaled once in build_model
-#ifndef CFM_SILU_PRE
-#define CFM_SILU_PRE 1   // 0: the plain SiLU / GLU epilogues in the 16-bit modes too (A/B builds)
-#endif
-template <typename T> constexpr bool kSiluPre = CFM_SILU_PRE && sizeof(T) == 2;
+template <typename T> constexpr bool kSiluPre = sizeof(T) == 2;
 template <typename T> constexpr int kActSilu = kSiluPre<T> ? ACT_SILU_L2E : ACT_SILU;
 constexpr float kLog2e = 1.4426950408889634f;
 
@@ -436,12 +433,11 @@ struct ModelT : public cfm_model {
           if (masked && use_ring_attention && dk == 64)
             r = chunk_attention_masked_bf16(w.q, w.kv, kv_rows, w.P + (size_t)l * d, p_rows, Lw.pu, Lw.pv,
                                             attd, aB, H, C, hh[PH_L] + C + hh[PH_R], w.ao, st, attn_diag, p_ld,
-                                            tune.attn_reuse, tune.attn_min_chunks);
+                                            tune.attn_min_chunks);
           else if (w.vt) {   // head_dim 128 (4-head d=512): V^T copy, then the band / score / P.V kernel
             KCHK(vt_transpose_bf16(w.kv, kv_rows, H, w.vt, w.vt_ld, st));
             r = chunk_attention_masked_a128(w.q, w.kv, kv_rows, w.vt, w.vt_ld, w.P + (size_t)l * d, p_rows, p_ld,
-                                            Lw.pu, Lw.pv, attd, aB, H, C, hh[PH_L] + C + hh[PH_R], w.ao, st,
-                                            tune.attn128_var);
+                                            Lw.pu, Lw.pv, attd, aB, H, C, hh[PH_L] + C + hh[PH_R], w.ao, st);
           }
           // full attention (padded plan, one chunk of T' per utterance: key window [0, T')) -> dense kernel
           else if (!masked && !stream && hh[PH_L] == 0 && hh[PH_R] == 0 && hh[PH_C] == hh[PH_TOUT] &&
@@ -452,8 +448,7 @@ struct ModelT : public cfm_model {
         if constexpr (std::is_same<T, f16>::value) {
           if (masked && use_ring_attention && dk == 64)
             r = chunk_attention_masked_f16(w.q, w.kv, kv_rows, w.P + (size_t)l * d, p_rows, Lw.pu, Lw.pv, attd, aB, H, C,
-                                           hh[PH_L] + C + hh[PH_R], w.ao, st, attn_diag, p_ld, tune.attn_reuse,
-                                           tune.attn_min_chunks);
+                                           hh[PH_L] + C + hh[PH_R], w.ao, st, attn_diag, p_ld, tune.attn_min_chunks);
         }
         if (r == -1)
           r = chunk_attention<T>(w.q, w.kv, kv_rows, w.P + (size_t)l * d, p_rows, Lw.pu, Lw.pv, attd, aB,
@@ -470,8 +465,7 @@ struct ModelT : public cfm_model {
       { EpiArgs e = E(SITE_PW1); e.bias = Lw.b_pw1; e.out = w.glu; e.ldo = d; e.row_off = gluoff;
         PROF(PC_PW1, gemm<T>(EPI_GLU, kSiluPre<T> ? ACT_SILU_L2E : ACT_NONE, w.h, d, (const T*)Lw.pw1, d, rB, 2 * d, d, e, st)); }
       if (cci && cco && !cfuse_out) PROF(PC_CACHE, cnn_cache_out<T>(w.glu, cache_start, d, 7, cco + l * cnn_ls, st));
-      PROF(PC_CONV, conv_dw_ln_silu<T>(w.glu, convd, vN, d, Lw.dw_t, Lw.b_dw, Lw.cn_w, Lw.cn_b, eps, w.cv, st,
-                                        tune.conv_dot2, tune.conv_dma));
+      PROF(PC_CONV, conv_dw_ln_silu<T>(w.glu, convd, vN, d, Lw.dw_t, Lw.b_dw, Lw.cn_w, Lw.cn_b, eps, w.cv, st));
       { EpiArgs e = E(SITE_PW2); e.bias = Lw.b_pw2; e.out = w.y; e.ldo = d;
         PROF(PC_PW2, gemm<T>(EPI_STORE, ACT_NONE, w.cv, d, (const T*)Lw.pw2, d, rN, d, d, e, st)); }
       // FFN (x 0.5); x + y_conv is not stored: norm_final re-applies it
@@ -653,7 +647,7 @@ static cfm_status build_model(const cfm_config& cfg, const HostW& hw, int device
       // the channel-stationary kernel's per-lane MFMA fragments ("fe_conv" >= 2), [tile][FE2_NFRAG][64 lanes]
       // x 16 B: W0 rows + b0 (bf16), the diagonal dw1 fragments of the 9 taps x 2 k-steps (bf16), the b1
       // seed in accumulator order (f32).  W0 and b0 are scaled by 2^-24 and w1 by 2^24 (exact), so conv0's
-      // accumulator carries 2^-24 x its value: the ReLU can then be a clamp to [0, 1] (frontend.hip FE2_CLAMP)
+      // accumulator carries 2^-24 x its value: the ReLU can then be a clamp to [0, 1] (frontend.hip fe2_relu_pk)
       if (d % 32 == 0) {
         std::vector<uint32_t> fr((size_t)(d / 32) * FE2_NFRAG * 64 * 4, 0u);
         // fp16 model: f16 fragments, unscaled (f16 has no exponent range for 2^-24; its kernel takes the
@@ -861,10 +855,8 @@ cfm_status cfm_model_set_option(cfm_model* m, const char* key, int64_t value) {
   {   // per-model kernel tuning / diagnostics; defaults are the measured best
     const std::pair<const char*, int*> knobs[] = {
         {"gemm_diag", &m->tune.gemm_diag}, {"gemm_wst", &m->tune.gemm_wst},   {"store_mode", &m->tune.store_mode},
-        {"col_group", &m->tune.col_group}, {"attn_reuse", &m->tune.attn_reuse}, {"conv_dot2", &m->tune.conv_dot2},
-        {"conv_dma", &m->tune.conv_dma},   {"dw2_seg", &m->tune.dw2_seg},   {"nt_sites", &m->tune.nt_sites},
+        {"col_group", &m->tune.col_group}, {"dw2_seg", &m->tune.dw2_seg},     {"nt_sites", &m->tune.nt_sites},
         {"fe_fuse_dw2", &m->tune.fe_fuse_dw2}, {"fe_conv", &m->tune.fe_conv},
-        {"attn128_var", &m->tune.attn128_var},
         {"gemm_big_min", &m->tune.big_min_tiles}, {"wsp_small_div", &m->tune.wsp_small_div},
         {"wsp_small_rows", &m->tune.wsp_small_rows},
         {"attn_min_chunks", &m->tune.attn_min_chunks}};
@@ -1044,10 +1036,10 @@ cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const 
   } else if (kernel == CFM_ATTN_RING) {
     if (dk == 64 && dtype == CFM_DTYPE_BF16)
       r = chunk_attention_masked_bf16((const bf16*)q, (const bf16*)kv, kv_rows, (const bf16*)P, p_rows, pos_u, pos_v, desc,
-                                      n_desc, H, C, W, (bf16*)out, st, 0, p_ld, 1, min_chunks);
+                                      n_desc, H, C, W, (bf16*)out, st, 0, p_ld, min_chunks);
     else if (dk == 64 && dtype == CFM_DTYPE_F16)
       r = chunk_attention_masked_f16((const f16*)q, (const f16*)kv, kv_rows, (const f16*)P, p_rows, pos_u, pos_v, desc,
-                                     n_desc, H, C, W, (f16*)out, st, 0, p_ld, 1, min_chunks);
+                                     n_desc, H, C, W, (f16*)out, st, 0, p_ld, min_chunks);
   } else if (kernel == CFM_ATTN_A128) {
     if (dtype == CFM_DTYPE_BF16 && attention_a128_eligible(C, W, p_rows, dk)) {
       if (!vt || vt_ld < kv_rows || vt_ld % 8) return set_error(CFM_ERR_VALUE, "attention: a128 needs vt [H * 128][vt_ld], vt_ld >= kv_rows, vt_ld % 8 == 0");

@@ -11,15 +11,9 @@
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 
-#ifndef LN_RPW
-#define LN_RPW 1    // A/B: rows per wave of the pre-norm LayerNorm kernel (1 or 2)
-#endif
 #ifndef LN2_RPW
 #define LN2_RPW 2   // rows per wave of the fused norm_final + next LayerNorm kernel: 2 interleaves two rows' loads and
                     // reductions (8.13 -> 8.06 ms/step for the LayerNorm class, profiles/r05_ab_ln2_rpw.txt); 1 = one
-#endif
-#ifndef LN_Y16
-#define LN_Y16 0   // A/B: 16-bit rows (d = 512) as one 16-B load / store per lane instead of two 8-B ones
 #endif
 
 namespace cfm {
@@ -76,10 +70,6 @@ CFM_DEV void store_row(H* p, const float (&v)[VPL]) {   // bf16 / f16 rows
   typedef H h4 __attribute__((ext_vector_type(4)));
   if constexpr (VPL == 2) {
     *reinterpret_cast<h2*>(p) = (h2){(H)v[0], (H)v[1]};
-  } else if constexpr (VPL == 8 && LN_Y16) {   // one 16-B store per lane
-    typedef H h8 __attribute__((ext_vector_type(8)));
-    __builtin_nontemporal_store((h8){(H)v[0], (H)v[1], (H)v[2], (H)v[3], (H)v[4], (H)v[5], (H)v[6], (H)v[7]},
-                                reinterpret_cast<h8*>(p));
   } else {
 #pragma unroll
     for (int e = 0; e < VPL; e += 4) {
@@ -95,11 +85,6 @@ CFM_DEV void load_row(const H* p, float (&v)[VPL]) {
   if constexpr (VPL == 2) {
     const h2 t = *reinterpret_cast<const h2*>(p);
     v[0] = (float)t[0]; v[1] = (float)t[1];
-  } else if constexpr (VPL == 8 && LN_Y16) {   // one 16-B load per lane
-    typedef H h8 __attribute__((ext_vector_type(8)));
-    const h8 t = __builtin_nontemporal_load(reinterpret_cast<const h8*>(p));
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
   } else {
 #pragma unroll
     for (int e = 0; e < VPL; e += 4) {
@@ -139,36 +124,6 @@ __global__ __launch_bounds__(256) void ln_kernel(float* __restrict__ x, ResidAdd
                                                  const uint8_t* __restrict__ rowmask) {
   const int lane = threadIdx.x & 63;
   constexpr int d = VPL * 64;
-  if constexpr (LN_RPW == 2) {   // A/B: two rows per wave (as ln2_kernel)
-    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;
-    if (row0 >= M) return;
-    const int row1 = row0 + 1 < M ? row0 + 1 : row0;
-    float v0[VPL], v1[VPL];
-    float* xp0 = x + (size_t)row0 * d + lane * VPL;
-    float* xp1 = x + (size_t)row1 * d + lane * VPL;
-    load_row(xp0, v0);
-    load_row(xp1, v1);
-    if (ra.y) {
-      resid_terms<T, VPL>(v0, ra, row0, lane);
-      resid_terms<T, VPL>(v1, ra, row1, lane);
-      if (!ra.defer) {
-        store_row(xp0, v0);
-        if (row1 != row0) store_row(xp1, v1);
-      }
-    }
-    ln_row<VPL>(v0, d, w, b, eps, lane);
-    ln_row<VPL>(v1, d, w, b, eps, lane);
-    if (rowmask) {
-#pragma unroll
-      for (int e = 0; e < VPL; ++e) {
-        if (!rowmask[row0]) v0[e] = 0.f;
-        if (!rowmask[row1]) v1[e] = 0.f;
-      }
-    }
-    store_row(out + (size_t)row0 * d + lane * VPL, v0);
-    if (row1 != row0) store_row(out + (size_t)row1 * d + lane * VPL, v1);
-    return;
-  }
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
   float v[VPL];
@@ -231,7 +186,7 @@ template <typename T>
 int layernorm(float* x, const ResidAdd<T>& ra, int M, int d, const float* w, const float* b, float eps, T* out,
               const uint8_t* rowmask, hipStream_t st) {
   if (M <= 0) return 0;
-  const int nblk = (M + 4 * LN_RPW - 1) / (4 * LN_RPW);
+  const int nblk = (M + 3) / 4;   // one row per wave
   if (d == 128) hipLaunchKernelGGL((ln_kernel<T, 2>), dim3(nblk), dim3(256), 0, st, x, ra, M, w, b, eps, out, rowmask);
   else if (d == 256) hipLaunchKernelGGL((ln_kernel<T, 4>), dim3(nblk), dim3(256), 0, st, x, ra, M, w, b, eps, out, rowmask);
   else if (d == 512) hipLaunchKernelGGL((ln_kernel<T, 8>), dim3(nblk), dim3(256), 0, st, x, ra, M, w, b, eps, out, rowmask);

@@ -361,3 +361,22 @@ def test_random_padded_batches_match_oracle(cfm, small_models, seed):
     out, m = small_models["fp32"].forward_encoder(xp, torch.tensor(lens), C, L, R)
     np.testing.assert_array_equal(m.cpu().numpy(), masks.numpy())
     np.testing.assert_allclose(out.cpu().numpy(), y.numpy(), atol=FP32_ATOL, rtol=0, err_msg=str((B, C, L, R)))
+
+
+def test_model_options_kept_and_retired(cfm):
+    """cfm_model_set_option: the keys of the retired kernel variants are unknown options (ValueError), every
+    key that tests, the Python package or a kernel still read is accepted at its default value.  On a model of
+    its own (SMALL: d = 128, 2 layers), so no other test sees the writes."""
+    from chunkformer_amd.config import SMALL
+    from chunkformer_amd.weights import synthetic_state_dict
+    enc = cfm.ChunkFormerEncoder(SMALL, synthetic_state_dict(SMALL, 1), dtype="bf16")
+    for key in ("attn128_var", "conv_dot2", "conv_dma", "attn_reuse"):
+        with pytest.raises(ValueError, match="unknown option"):
+            enc.set_option(key, 1)
+    defaults = {"ring_attention": 1, "fe_conv": 6, "fe_fuse_dw2": 1, "gemm_wst": 1, "fe_group_windows": 0,
+                "wsp_small_div": 1, "wsp_small_rows": 32768, "attn_min_chunks": 2, "gemm_big_min": 0,
+                "cache_fuse": 1, "ctc_fused": 1, "trim_right": 0, "fe_carry": 0, "fe_reuse": 0, "fe_save_from": -1,
+                "profile": 0, "profile_reset": 0, "max_layers": -1,
+                "nt_sites": 8, "store_mode": 0, "col_group": 0, "dw2_seg": 4, "attn_diag": 0, "gemm_diag": 0}
+    for key, value in defaults.items():
+        enc.set_option(key, value)

@@ -1,5 +1,5 @@
 """LDS layout invariants of the ring attention kernel's rel_shift scratch (chunkformer_amd/csrc/attention.hip,
-`skew_slot` / `skew_half`), checked on the CPU against the banking model of MI355X_MICROARCH.md §LDS: the 16-lane
+`skew_slot` / `skew_issue`), checked on the CPU against the banking model of MI355X_MICROARCH.md §LDS: the 16-lane
 groups of ds_write_b64 and the 32-lane groups of ds_read_b32 / ds_read2_b32 take one LDS cycle when their dwords hit
 distinct banks ((a/4) mod 32).  The permuted row order is what removed the read side's 2-way conflicts (DESIGN §5,
 round 6); a table edit that breaks the property fails here, without a GPU."""
@@ -10,7 +10,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "chunkformer_amd", "csrc", "attention.hip")
-RD_PITCH = 52   # ATTN_RD_PITCH (bf16 elements per scratch row)
+RD_PITCH = 52   # attention.hip RD_PITCH (bf16 elements per scratch row)
 
 
 def _slot_table():

@@ -1,7 +1,7 @@
 """Build an A/B variant of libcfm.so: the listed sources recompiled with extra -D flags, every
 other object taken from chunkformer_amd/_build/ (build the product first).
 
-    python tools/build_variant.py TAG gemm_wst.hip -DWSP_LGKM=0 [-DCFM_GEMM_DIAG ...]
+    python tools/build_variant.py TAG gemm_wst_dw2.hip -DDW2_BARP=4 [-DCFM_GEMM_DIAG ...]
 
 writes chunkformer_amd/_build/variants/libcfm_TAG.so; select it with CFM_LIB=<path> (chunkformer_amd/_lib.py).
 """
