@@ -17,6 +17,10 @@ split, chunkformer/utils/model_utils.py:23-221) runs on the device (cfm_ctc_coll
 the id -> text mapping (class2str) and the hh:mm:ss:ms formatting stay on the host, so
 `char_dict` models return strings like the reference.
 
+Hybrid CTC / attention checkpoints (`decoder: transformer` / `bitransformer` with decoder.* tensors) also
+decode with `decoding_method="attention_rescoring"` (asr_model.py:326-343): the prefix beam search's n-best
+rescored by the attention decoder on the device (rescore.py, cfm_aed_score).
+
 `model: transducer` checkpoints (config.yaml, init_model.py:118-135) decode with the RNN-T greedy
 search on the device (transducer.py, cfm_rnnt_greedy) exactly where the reference calls
 optimized_search / batch_greedy_search (chunkformer_model.py:439-448, 533-543); their per-frame
@@ -47,6 +51,7 @@ from .config import EncoderConfig
 from .encoder import ChunkFormerEncoder
 from .streaming import EndlessGraphPipeline, EndlessGraphRunner, EndlessPipeline
 from .classifier import ClassifierConfig, ClassifierHeads
+from .rescore import AEDConfig, AttentionRescorer
 from .transducer import RNNTConfig, RNNTGreedy
 
 Features = Union[torch.Tensor, np.ndarray, str]
@@ -201,7 +206,7 @@ class ChunkFormerModel:
                  resample_conf: Optional[dict] = None, model_type: str = "asr_model",
                  rnnt_config: Optional[RNNTConfig] = None, tasks: Optional[Dict[str, int]] = None,
                  classifier_config: Optional[ClassifierConfig] = None,
-                 label_mapping: Optional[Dict[str, Dict[str, str]]] = None):
+                 label_mapping: Optional[Dict[str, Dict[str, str]]] = None, aed_config: Optional[AEDConfig] = None):
         if model_type not in ("asr_model", "transducer", "classification"):
             raise AssertionError(f"model: {model_type} is not one of asr_model / transducer / classification")
         self.is_classification = model_type == "classification"
@@ -223,6 +228,10 @@ class ChunkFormerModel:
         self.classifier = None
         if self.is_classification:
             self.classifier = ClassifierHeads(classifier_config, state_dict, self.device)
+        # the attention decoder of a hybrid CTC / attention checkpoint (decoding_method "attention_rescoring")
+        self.rescorer = None
+        if aed_config is not None and model_type == "asr_model":
+            self.rescorer = AttentionRescorer(aed_config, state_dict, self.device, dtype)
         self.label_mapping = label_mapping
         self.char_dict = char_dict
         self.fbank_conf = dict(fbank_conf or {})
@@ -311,6 +320,12 @@ class ChunkFormerModel:
                                               output_dim=vocab, cmvn=has_cmvn)
         rnnt_cfg = RNNTConfig.from_conf(conf, vocab, cfg.d_model) if model_type == "transducer" else None
         cls_cfg = ClassifierConfig.from_conf(conf, cfg.d_model) if model_type == "classification" else None
+        # init_model.py:81-98: an asr_model checkpoint with decoder.* tensors carries the attention decoder that
+        # attention_rescoring runs; unsupported decoder settings raise AssertionError here
+        aed_cfg = None
+        if (model_type == "asr_model" and any(k.startswith("decoder.") for k in sd)
+                and conf.get("decoder", "transformer") in ("transformer", "bitransformer")):
+            aed_cfg = AEDConfig.from_conf(conf, vocab, cfg.d_model)
         label_mapping = None
         lp = os.path.join(path, "label_mapping.json")
         if os.path.exists(lp):
@@ -328,7 +343,7 @@ class ChunkFormerModel:
                     char_dict[int(arr[1])] = arr[0]
         return cls(cfg, sd, dtype=dtype, device=device, char_dict=char_dict, fbank_conf=conf.get("fbank_conf"),
                    resample_conf=conf.get("resample_conf"), model_type=model_type, rnnt_config=rnnt_cfg,
-                   classifier_config=cls_cfg, label_mapping=label_mapping)
+                   classifier_config=cls_cfg, label_mapping=label_mapping, aed_config=aed_cfg)
 
     def get_tasks(self) -> Optional[Dict[str, int]]:
         """chunkformer_model.py:250-254: {task: classes} of a classification model, else None."""
@@ -348,15 +363,20 @@ class ChunkFormerModel:
                              "checkpoint. Use classify / classify_audio / batch_classify instead.")
 
     def _beam_method(self, decoding_method: str) -> bool:
-        """True for "ctc_prefix_beam_search" (CTC checkpoints only), False for the greedy default."""
+        """True for "ctc_prefix_beam_search" and "attention_rescoring" (CTC checkpoints only; the latter needs the
+        checkpoint's attention decoder), False for the greedy default."""
         if decoding_method == "ctc_greedy_search":
             return False
-        if decoding_method != "ctc_prefix_beam_search":
-            raise ValueError(f"unknown decoding_method {decoding_method!r}: ctc_greedy_search or "
-                             "ctc_prefix_beam_search")
+        if decoding_method not in ("ctc_prefix_beam_search", "attention_rescoring"):
+            raise ValueError(f"unknown decoding_method {decoding_method!r}: ctc_greedy_search, "
+                             "ctc_prefix_beam_search or attention_rescoring")
         if self.model_type == "transducer":
-            raise ValueError("This model is a transducer model: ctc_prefix_beam_search needs an asr_model "
+            raise ValueError(f"This model is a transducer model: {decoding_method} needs an asr_model "
                              "checkpoint. Its decoding is the RNN-T greedy search.")
+        if decoding_method == "attention_rescoring" and getattr(self, "rescorer", None) is None:
+            raise ValueError("This model has no attention decoder (the checkpoint holds no decoder.* tensors): "
+                             "attention_rescoring needs a hybrid CTC / attention checkpoint. Use "
+                             "ctc_prefix_beam_search or ctc_greedy_search.")
         return True
 
     # ---------------------------------------------------------------- API
@@ -374,7 +394,8 @@ class ChunkFormerModel:
                        max_silence_duration: float = 0.5, return_encoder_out: bool = False,
                        cuda_graph: bool = True, pipeline: Optional[bool] = None,
                        pipeline_depth: Optional[int] = None, decoding_method: str = "ctc_greedy_search",
-                       beam_size: int = 10, context_graph=None, return_nbest: bool = False):
+                       beam_size: int = 10, context_graph=None, return_nbest: bool = False,
+                       ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None):
         """chunkformer_model.py:321-459.  Segments of `total_batch_duration` seconds (halved,
         like the reference) go through forward_parallel_chunk with the attention/conv caches
         and `offset` carried; the CTC argmax runs per segment on the kept rows (row-wise, so
@@ -391,9 +412,13 @@ class ChunkFormerModel:
         decoding_method "ctc_prefix_beam_search": the runner returns the encoder rows, and the top-k and
         beam kernels run over their concatenation as one utterance (`beam_size`, `context_graph`); the
         sentence split then places the best hypothesis' tokens at their `times` frames.
-        `return_nbest`: the n-best texts (or the DecodeResult without a char_dict)."""
+        `return_nbest`: the n-best texts (or the DecodeResult without a char_dict).
+        decoding_method "attention_rescoring": that n-best rescored by the attention decoder over the same
+        concatenated rows (rescore.py; `ctc_weight` / `reverse_weight` default to the checkpoint's model_conf);
+        with `return_nbest` the n-best comes back re-ranked by the rescored totals."""
         self._require_asr("endless_decode")
         beam = self._beam_method(decoding_method)
+        rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -467,6 +492,8 @@ class ChunkFormerModel:
             enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
             T = enc_all.shape[0]
             best = enc.ctc_prefix_beam_search(enc_all, [0], [T], beam_size, context_graph)[0]
+            if rescoring:
+                best = self.rescorer.rescore([best], enc_all, [0], [T], ctc_weight, reverse_weight, return_nbest)[0]
             if self.char_dict is None:
                 res = best
             elif return_nbest:
@@ -502,14 +529,20 @@ class ChunkFormerModel:
     def batch_decode(self, audio_paths: List[Features], chunk_size: Optional[int] = 64,
                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
                      total_batch_duration: int = 1800, decoding_method: str = "ctc_greedy_search",
-                     beam_size: int = 10, context_graph=None, return_nbest: bool = False):
+                     beam_size: int = 10, context_graph=None, return_nbest: bool = False,
+                     ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None):
         """chunkformer_model.py:462-552 (asr_model branch): budget grouping, one masked-batch
         encoder call per group, CTC argmax, per-utterance split to its subsampled length.
         decoding_method "ctc_prefix_beam_search": one top-k and one beam-search call per masked batch over
         the same per-utterance row ranges (`beam_size`, `context_graph`: search.ContextGraph); text of the
-        best hypothesis (`return_nbest`: of every hypothesis), or DecodeResults without a char_dict."""
+        best hypothesis (`return_nbest`: of every hypothesis), or DecodeResults without a char_dict.
+        decoding_method "attention_rescoring" (asr_model.py:326-343): the same top-k and beam search, then one
+        attention decoder call per masked batch over the packed encoder rows it already holds, scoring every
+        hypothesis of every utterance (rescore.py); `ctc_weight` / `reverse_weight` default to the checkpoint's
+        model_conf; with `return_nbest` the n-best comes back re-ranked by the rescored totals."""
         self._require_asr("batch_decode")
         beam = self._beam_method(decoding_method)
+        rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -539,8 +572,12 @@ class ChunkFormerModel:
                 continue
             if beam:
                 starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
-                for r in self.encoder.ctc_prefix_beam_search(eo.reshape(-1, eo.shape[-1]), starts, el_ctc, beam_size,
-                                                             context_graph):
+                rows = eo.reshape(-1, eo.shape[-1])
+                results = self.encoder.ctc_prefix_beam_search(rows, starts, el_ctc, beam_size, context_graph)
+                if rescoring:
+                    results = self.rescorer.rescore(results, rows, starts, el_ctc, ctc_weight, reverse_weight,
+                                                    return_nbest)
+                for r in results:
                     if self.char_dict is None:
                         decodes.append(r)
                     elif return_nbest:

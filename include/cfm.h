@@ -426,6 +426,60 @@ cfm_status cfm_cls_classify(const cfm_cls* h, const float* enc_dev, int32_t rows
                             float* prob_dev /* [B, n_tasks] f32 */, void* workspace, size_t workspace_bytes,
                             cfm_stream stream);
 
+/* ---- attention decoder consumer (model: hybrid CTC / attention checkpoints, `decoder: transformer` /
+ * `bitransformer`): the left-to-right and right-to-left TransformerDecoder (modules/decoder.py:35-226, 330-484;
+ * normalize_before, relu, position-wise feed-forward, all biases, dropout off) scoring the CTC prefix beam n-best
+ * against the encoder output, as attention_rescoring consumes it (modules/search.py:358-439 over
+ * asr_model.py:399-492).  Semantics: DESIGN.md 9d.  compute dtype: F32 = exact-f32 GEMMs and the generic segment
+ * attention kernel; BF16 / F16 = 16-bit GEMMs (f32 accumulate) and the MFMA segment attention kernel at head dim
+ * 64 / 128 (other head dims: the generic kernel on 16-bit rows).  Embedding, residual stream, LayerNorm statistics,
+ * softmax and the log-sum-exp are f32 in every mode. */
+typedef struct {
+  int32_t d;             /* encoder output_size = the decoder's attention dim; a multiple of 64 */
+  int32_t H;             /* decoder_conf.attention_heads; head dim d / H a multiple of 16 up to 128 */
+  int32_t ff;            /* decoder_conf.linear_units; a multiple of 64 */
+  int32_t num_blocks;    /* decoder_conf.num_blocks */
+  int32_t r_num_blocks;  /* decoder_conf.r_num_blocks (read when the right decoder's weights are given) */
+  int32_t V;             /* output_dim */
+  float eps;             /* decoder_conf.norm_eps (1e-5) */
+  int32_t sos, eos;      /* asr_model.py:49-58 */
+  int32_t dtype;         /* cfm_dtype */
+} cfm_aed_config;
+typedef struct cfm_aed cfm_aed;
+
+/* weights by reference key: decoder.left_decoder.* and, for a bitransformer, decoder.right_decoder.*:
+ *   embed.0.weight [V, d], after_norm.{weight,bias}, output_layer.{weight,bias},
+ *   decoders.{i}.{self_attn,src_attn}.linear_{q,k,v,out}.{weight,bias}, decoders.{i}.feed_forward.w_{1,2}.{weight,bias},
+ *   decoders.{i}.norm{1,2,3}.{weight,bias}
+ * (a `decoder: transformer` checkpoint's decoder.* tensors are passed under the left decoder's names; without
+ * decoder.right_decoder.embed.0.weight the handle has no right decoder).  Repacked once: Q [d, d], K|V [2d, d] for
+ * self- and cross-attention, 16-bit copies in the 16-bit modes; other keys (embed.1.pe among them: the
+ * positional table is computed) are ignored.  Missing / mis-sized keys -> CFM_ERR_VALUE. */
+cfm_status cfm_aed_create(const cfm_aed_config* cfg, const cfm_tensor_view* weights, int32_t n_weights, int32_t device,
+                          cfm_aed** out);
+void cfm_aed_destroy(cfm_aed* h);
+size_t cfm_aed_workspace_bytes(const cfm_aed* h, int32_t tokens, int32_t mem_rows);
+/* Scores every hypothesis of every utterance of a batch in one call.  Utterance u = rows [utt_row_start[u],
+ * + utt_row_len[u]) of mem_dev [mem_rows, d] f32 (device int32 arrays as in cfm_ctc_collapse; zero rows: the
+ * cross-attention context is exactly zero).  Hypothesis h = the packed token rows [hyp_start[h], + hyp_len[h]) of
+ * tokens_dev [tokens] int32, hyp_len = its n tokens + 1: row 0 is the sos row (its content is ignored), row 1 + i
+ * holds token i; hyp_utt[h] names its utterance.  Each hypothesis is a causal segment of its own (the reference's
+ * padded batch with masked padding computes the same).  direction_mask bit 0: left to right, bit 1: right to left
+ * (input [sos, token n-1 .. token 0], read in reverse by index; CFM_ERR_ASSERT without a right decoder).  Outputs,
+ * f32 [tokens] per direction: out[hyp_start + j] = the log-prob of row j's target in that direction's own order --
+ * its next input token, eos on the last row.  The per-hypothesis sums, the combination with the CTC score and the
+ * argmax are the caller's (Python float64).
+ * The first int32 of the workspace is a status word, zero after a complete call (1: a hypothesis' row range outside
+ * [0, tokens), empty or longer than 5000; 2: its utterance index or the utterance's row range outside their arrays;
+ * 3: a token id outside [0, V)); read it after the stream has completed.  A rejected hypothesis is skipped (its
+ * output rows are untouched, nothing is read out of range); the others are scored as without it.  Rows of no
+ * hypothesis are never written.  Stream-ordered, caller-allocated: no allocation, no host synchronisation. */
+cfm_status cfm_aed_score(const cfm_aed* h, const float* mem_dev, int32_t mem_rows, const int32_t* utt_row_start_dev,
+                         const int32_t* utt_row_len_dev, int32_t B, const int32_t* tokens_dev, int32_t tokens,
+                         const int32_t* hyp_start_dev, const int32_t* hyp_len_dev, const int32_t* hyp_utt_dev,
+                         int32_t n_hyps, int32_t direction_mask, float* tok_logp_l2r_dev, float* tok_logp_r2l_dev,
+                         void* workspace, size_t workspace_bytes, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,23 @@ cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const 
                             int32_t n_desc, int32_t H, int32_t dk, int32_t C, int32_t W, void* out, int32_t min_chunks,
                             void* vt, int32_t vt_ld, int32_t nutt, int32_t nd, int32_t t_keys, cfm_stream stream);
 
+/* One segment attention kernel of the attention decoder on caller-owned buffers (csrc/aed.hip).  `kernel` names the
+ * kernel and nothing else runs in its place: a configuration the selected kernel does not take launches nothing,
+ * leaves `out` untouched and returns CFM_ERR_ASSERT naming the kernel.
+ *   q [q_rows][H*dk], out [q_rows][H*dk], kv [k_rows][K (H*dk) | V (H*dk)] (dtype elements), head h at column h*dk
+ *   of each part; desc [n_seg][8] int32 on the device: (Q0, NQ, K0, NK, CAUSAL, 0, 0, 0).  For segment s, head h,
+ *   query i < NQ (row Q0 + i) and the keys j < NK (row K0 + j) it sees -- all of them, or j <= i when CAUSAL:
+ *     out_i = softmax_j(q_i . k_j / sqrt(dk)) . V      (f32 online softmax; no visible key: a zero row)
+ *   Rows that no descriptor covers are neither read nor written.  Query ranges must not overlap.
+ * GENERIC: f32 / bf16 / f16, dk a multiple of 16 up to 128.   MFMA: bf16 / f16, dk 64 or 128.
+ * scratch: n_seg + 2 int32 on the device: [0] a status word, zero after the call unless a descriptor's range lies
+ * outside its array (1; that segment is skipped) or the segments hold more query tiles than q_rows allows (4);
+ * [1 ..] the segments' tile offsets. */
+typedef enum { CFM_SEG_ATTN_GENERIC = 0, CFM_SEG_ATTN_MFMA = 1 } cfm_seg_attn_kernel;
+cfm_status cfm_op_seg_attention(int32_t dtype, int32_t kernel, const void* q, int32_t q_rows, const void* kv,
+                                int32_t k_rows, const int32_t* desc, int32_t n_seg, int32_t H, int32_t dk, void* out,
+                                int32_t* scratch, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
