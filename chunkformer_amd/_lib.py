@@ -146,15 +146,23 @@ cfm_aed_create = _sig("cfm_aed_create", I32, ctypes.POINTER(CfmAedConfig), ctype
 cfm_aed_destroy = _sig("cfm_aed_destroy", None, P)
 cfm_aed_workspace_bytes = _sig("cfm_aed_workspace_bytes", SZ, P, I32, I32)
 cfm_aed_score = _sig("cfm_aed_score", I32, P, P, I32, P, P, I32, P, I32, P, P, P, I32, I32, P, P, P, SZ, P)
+# attention decoding mode over the same handle (csrc/attdec.hip)
+cfm_attdec_workspace_bytes = _sig("cfm_attdec_workspace_bytes", SZ, P, I32, I32, I32, I32)
+cfm_attdec_begin = _sig("cfm_attdec_begin", I32, P, P, I32, P, P, P, I32, I32, I32, P, SZ, P)
+cfm_attdec_steps = _sig("cfm_attdec_steps", I32, P, P, I32, I32, I32, I32, I32, I32, P)
+cfm_attdec_finish = _sig("cfm_attdec_finish", I32, P, P, I32, I32, I32, I32, ctypes.c_float, P, P, P, P, P, P, P, P)
 # include/cfm_ops.h
 SEG_ATTN_GENERIC, SEG_ATTN_MFMA = 0, 1
+DEC_ATTN_SELF_GATHER, DEC_ATTN_CROSS_GENERIC, DEC_ATTN_CROSS_MFMA = 0, 1, 2
+cfm_op_decode_attention = _sig("cfm_op_decode_attention", I32, I32, I32, P, P, I32, I32, I32, I32, P, I32, P, I32, I32, P,
+                               P, I32, P, P)
 cfm_op_seg_attention = _sig("cfm_op_seg_attention", I32, I32, I32, P, I32, P, I32, P, I32, I32, I32, P, P, P)
 cfm_op_gemm = _sig("cfm_op_gemm", I32, I32, I32, I32, P, I32, P, I32, I32, I32, I32, P, ctypes.c_float, P, I32, I32, P,
                    I32, P, I32, P, I32, P)
 ATTN_GENERIC, ATTN_RING, ATTN_A128, ATTN_DENSE = 0, 1, 2, 3
 cfm_op_attention = _sig("cfm_op_attention", I32, I32, I32, P, P, I32, P, I32, I32, P, P, P, I32, I32, I32, I32, I32, P,
                         I32, P, I32, I32, I32, I32, P)
-EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_seg_attention"]
+EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_seg_attention", "cfm_op_decode_attention"]
 
 EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_destroy", "cfm_model_set_option",
             "cfm_plan_masked", "cfm_plan_masked_ex", "cfm_plan_padded", "cfm_workspace_bytes_masked", "cfm_workspace_bytes_padded",
@@ -169,7 +177,8 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_ctc_topk_workspace_bytes", "cfm_ctc_topk_slab_rows", "cfm_ctc_topk", "cfm_ctc_topk_logp",
             "cfm_ctx_create", "cfm_ctx_destroy", "cfm_ctc_beam_workspace_bytes", "cfm_ctc_beam_search",
             "cfm_ctc_align_plan", "cfm_ctc_align",
-            "cfm_aed_create", "cfm_aed_destroy", "cfm_aed_workspace_bytes", "cfm_aed_score"]
+            "cfm_aed_create", "cfm_aed_destroy", "cfm_aed_workspace_bytes", "cfm_aed_score",
+            "cfm_attdec_workspace_bytes", "cfm_attdec_begin", "cfm_attdec_steps", "cfm_attdec_finish"]
 
 
 def profile_read(h):

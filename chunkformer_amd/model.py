@@ -232,6 +232,7 @@ class ChunkFormerModel:
         self.rescorer = None
         if aed_config is not None and model_type == "asr_model":
             self.rescorer = AttentionRescorer(aed_config, state_dict, self.device, dtype)
+        self._attention_decoder = None   # decoding_method "attention": built on first use over the rescorer's handle
         self.label_mapping = label_mapping
         self.char_dict = char_dict
         self.fbank_conf = dict(fbank_conf or {})
@@ -362,6 +363,21 @@ class ChunkFormerModel:
             raise ValueError(f"This model is a classification model: {what} needs an asr_model or transducer "
                              "checkpoint. Use classify / classify_audio / batch_classify instead.")
 
+    def _attention_search(self):
+        """The AttentionDecoder of decoding_method "attention" (attention_decode.py), over the rescorer's handle: the
+        decoder weights are on the device once.  ValueError for a transducer model or a checkpoint without decoder."""
+        if self.model_type == "transducer":
+            raise ValueError("This model is a transducer model: attention needs an asr_model checkpoint with an "
+                             "attention decoder. Its decoding is the RNN-T greedy search.")
+        if getattr(self, "rescorer", None) is None:
+            raise ValueError("This model has no attention decoder (the checkpoint holds no decoder.* tensors): "
+                             "attention needs a hybrid CTC / attention checkpoint. Use ctc_prefix_beam_search or "
+                             "ctc_greedy_search.")
+        if getattr(self, "_attention_decoder", None) is None:
+            from .attention_decode import AttentionDecoder
+            self._attention_decoder = AttentionDecoder(self.rescorer)
+        return self._attention_decoder
+
     def _beam_method(self, decoding_method: str) -> bool:
         """True for "ctc_prefix_beam_search" and "attention_rescoring" (CTC checkpoints only; the latter needs the
         checkpoint's attention decoder), False for the greedy default."""
@@ -395,7 +411,8 @@ class ChunkFormerModel:
                        cuda_graph: bool = True, pipeline: Optional[bool] = None,
                        pipeline_depth: Optional[int] = None, decoding_method: str = "ctc_greedy_search",
                        beam_size: int = 10, context_graph=None, return_nbest: bool = False,
-                       ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None):
+                       ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
+                       length_penalty: float = 0.0, max_len: Optional[int] = None):
         """chunkformer_model.py:321-459.  Segments of `total_batch_duration` seconds (halved,
         like the reference) go through forward_parallel_chunk with the attention/conv caches
         and `offset` carried; the CTC argmax runs per segment on the kept rows (row-wise, so
@@ -415,9 +432,15 @@ class ChunkFormerModel:
         `return_nbest`: the n-best texts (or the DecodeResult without a char_dict).
         decoding_method "attention_rescoring": that n-best rescored by the attention decoder over the same
         concatenated rows (rescore.py; `ctc_weight` / `reverse_weight` default to the checkpoint's model_conf);
-        with `return_nbest` the n-best comes back re-ranked by the rescored totals."""
+        with `return_nbest` the n-best comes back re-ranked by the rescored totals.
+        decoding_method "attention": the attention decoder's own beam search (attention_decode.py; `beam_size`,
+        `length_penalty`, `max_len`) over the concatenated rows as one utterance; more than 5,000 rows need
+        `max_len`.  The hypothesis carries no frame times: the text comes back as one string (the DecodeResult
+        without a char_dict; `return_nbest`: the N final hypotheses in final-score order)."""
         self._require_asr("endless_decode")
-        beam = self._beam_method(decoding_method)
+        attention = decoding_method == "attention"
+        searcher = self._attention_search() if attention else None
+        beam = False if attention else self._beam_method(decoding_method)
         rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
@@ -429,7 +452,7 @@ class ChunkFormerModel:
         ids, outs = [], []
         seg_len = max(stop - start for start, stop, _, _ in segs) if segs else 0
         transducer = self.model_type == "transducer"
-        want_eo = bool(return_encoder_out) or transducer or beam   # the searches consume the encoder rows
+        want_eo = bool(return_encoder_out) or transducer or beam or attention   # the searches consume the encoder rows
         if pipeline is None:
             pipeline = len(segs) >= 3
         if pipeline_depth is None:
@@ -488,6 +511,18 @@ class ChunkFormerModel:
             if return_encoder_out:
                 return res, enc_all.unsqueeze(0)
             return res
+        if attention:
+            enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
+            best = searcher.search(enc_all, [0], [enc_all.shape[0]], beam_size, length_penalty, max_len)[0]
+            if self.char_dict is None:
+                res = best
+            elif return_nbest:
+                res = [class2str(h, self.char_dict).strip() for h in best.nbest]
+            else:
+                res = class2str(best.tokens, self.char_dict).strip()
+            if return_encoder_out:
+                return res, enc_all.unsqueeze(0)
+            return res
         if beam:
             enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
             T = enc_all.shape[0]
@@ -530,7 +565,8 @@ class ChunkFormerModel:
                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
                      total_batch_duration: int = 1800, decoding_method: str = "ctc_greedy_search",
                      beam_size: int = 10, context_graph=None, return_nbest: bool = False,
-                     ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None):
+                     ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
+                     length_penalty: float = 0.0, max_len: Optional[int] = None):
         """chunkformer_model.py:462-552 (asr_model branch): budget grouping, one masked-batch
         encoder call per group, CTC argmax, per-utterance split to its subsampled length.
         decoding_method "ctc_prefix_beam_search": one top-k and one beam-search call per masked batch over
@@ -539,9 +575,14 @@ class ChunkFormerModel:
         decoding_method "attention_rescoring" (asr_model.py:326-343): the same top-k and beam search, then one
         attention decoder call per masked batch over the packed encoder rows it already holds, scoring every
         hypothesis of every utterance (rescore.py); `ctc_weight` / `reverse_weight` default to the checkpoint's
-        model_conf; with `return_nbest` the n-best comes back re-ranked by the rescored totals."""
+        model_conf; with `return_nbest` the n-best comes back re-ranked by the rescored totals.
+        decoding_method "attention" (asr_model.py's `attention` mode): the attention decoder's own beam search
+        (attention_decode.py), one device search per masked batch over the same packed rows, every utterance
+        stopping at its own row count (or `max_len`); `beam_size` (1 .. 16), `length_penalty`."""
         self._require_asr("batch_decode")
-        beam = self._beam_method(decoding_method)
+        attention = decoding_method == "attention"
+        searcher = self._attention_search() if attention else None
+        beam = False if attention else self._beam_method(decoding_method)
         rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
@@ -569,6 +610,17 @@ class ChunkFormerModel:
                     decodes.extend(class2str(h, self.char_dict).strip() for h in hyps)
                 else:
                     decodes.extend(hyps)
+                continue
+            if attention:
+                starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+                results = searcher.search(eo.reshape(-1, eo.shape[-1]), starts, el_ctc, beam_size, length_penalty, max_len)
+                for r in results:
+                    if self.char_dict is None:
+                        decodes.append(r)
+                    elif return_nbest:
+                        decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
+                    else:
+                        decodes.append(class2str(r.tokens, self.char_dict).strip())
                 continue
             if beam:
                 starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()

@@ -480,6 +480,35 @@ cfm_status cfm_aed_score(const cfm_aed* h, const float* mem_dev, int32_t mem_row
                          int32_t n_hyps, int32_t direction_mask, float* tok_logp_l2r_dev, float* tok_logp_r2l_dev,
                          void* workspace, size_t workspace_bytes, cfm_stream stream);
 
+/* ---- attention decoding mode over the same handle: the reference's autoregressive attention_beam_search
+ * (modules/search.py:252-355) with the left decoder, every utterance of a masked batch at once, `beam` (1 .. 16, at
+ * most V) rows each; row r = u * beam + j.  Semantics: DESIGN.md 9e.  All running utterances step together (step i
+ * feeds position i - 1); an utterance stops after its own limit[u] steps or once all its beams ended with eos, and is
+ * frozen from then on.  The geometry (B, beam, mem_rows, max_steps) names the layout of the caller-allocated state
+ * and must be the same in every call on it; max_steps <= 5000 bounds the self-attention cache and the trace.
+ * The first int32 of the state is a status word (0; 2: an utterance's row range outside the encoder rows; 5: a
+ * limit outside [0, max_steps]; such an utterance is skipped, the others are unaffected), the second the number of
+ * utterances still running; read them after the stream has completed.  Scores accumulate in f32. */
+size_t cfm_attdec_workspace_bytes(const cfm_aed* h, int32_t B, int32_t beam, int32_t mem_rows, int32_t max_steps);
+/* Validates the utterance row ranges [utt_row_start[u], + utt_row_len[u]) of mem_dev [mem_rows, d] f32 and the limits
+ * on the device, projects the cross-attention K|V of every left-decoder block once over all encoder rows, and
+ * writes the start state: hypotheses [sos], scores [0, -inf, ...].  The three int32 arrays are device arrays [B]. */
+cfm_status cfm_attdec_begin(const cfm_aed* h, const float* mem_dev, int32_t mem_rows, const int32_t* utt_row_start_dev,
+                            const int32_t* utt_row_len_dev, const int32_t* limit_dev, int32_t B, int32_t beam,
+                            int32_t max_steps, void* state, size_t state_bytes, cfm_stream stream);
+/* Steps first_step .. first_step + n_steps - 1 (1-based, consecutive over the calls, at most max_steps).
+ * Stream-ordered: no allocation, no host synchronisation; steps of frozen utterances change nothing. */
+cfm_status cfm_attdec_steps(const cfm_aed* h, void* state, int32_t B, int32_t beam, int32_t mem_rows, int32_t max_steps,
+                            int32_t first_step, int32_t n_steps, cfm_stream stream);
+/* Backtrace and selection.  tokens [B * beam, max_steps] int32: row r's lengths[r] tokens after the sos (eos tokens
+ * included); final_scores [B * beam] f32 = score / (count of tokens != eos over the row, sos included)^length_penalty;
+ * best [B]: the first maximum (a NaN counts as the maximum).  Optional trace [max_steps, B * beam] of (parent beam,
+ * token, score) per step; rows of steps an utterance did not take hold (-1, -1, 0). */
+cfm_status cfm_attdec_finish(const cfm_aed* h, void* state, int32_t B, int32_t beam, int32_t mem_rows, int32_t max_steps,
+                             float length_penalty, int32_t* tokens_dev, int32_t* lengths_dev, float* final_scores_dev,
+                             int32_t* best_dev, int32_t* trace_parent_dev, int32_t* trace_token_dev,
+                             float* trace_score_dev, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,23 @@ cfm_status cfm_op_seg_attention(int32_t dtype, int32_t kernel, const void* q, in
                                 int32_t k_rows, const int32_t* desc, int32_t n_seg, int32_t H, int32_t dk, void* out,
                                 int32_t* scratch, cfm_stream stream);
 
+/* One attention kernel of the attention decoding mode on caller-owned buffers (csrc/attdec.hip).  `kernel` names the
+ * kernel and nothing else runs in its place (CFM_ERR_ASSERT naming it for a configuration it does not take).
+ * Rows r = u * beam + j, R = B * beam, beam <= 16; q, out [R][H*dk] (dtype elements), head h at column h*dk.
+ *   SELF_GATHER (f32 / bf16 / f16, dk a multiple of 16 up to 128): kv [kv_rows positions][R][K (H*dk) | V (H*dk)];
+ *     row r attends over n_keys (1 .. kv_rows) positions: position p < n_keys - 1 is read from slot
+ *     ancestry[r * ancestry_ld + p] (a row index), position n_keys - 1 from slot r.
+ *   CROSS_GENERIC (as above) / CROSS_MFMA (bf16 / f16, dk 64 or 128): kv [kv_rows][K | V]; the beams of utterance u
+ *     attend over its rows [utt_start[u], + utt_len[u]) (device int32 [B]; none, or a range outside kv: a zero row),
+ *     split into n_split (1 .. 16) key parts merged by their (m, l, o); scratch: n_split * R * (H*dk + 2 H) f32
+ *     (unused with one part).
+ *   out_r = softmax_j(q_r . k_j / sqrt(dk)) . V, f32 online softmax. */
+typedef enum { CFM_DEC_ATTN_SELF_GATHER = 0, CFM_DEC_ATTN_CROSS_GENERIC = 1, CFM_DEC_ATTN_CROSS_MFMA = 2 } cfm_dec_attn_kernel;
+cfm_status cfm_op_decode_attention(int32_t dtype, int32_t kernel, const void* q, void* out, int32_t B, int32_t beam,
+                                   int32_t H, int32_t dk, const void* kv, int32_t kv_rows, const int32_t* ancestry,
+                                   int32_t ancestry_ld, int32_t n_keys, const int32_t* utt_start, const int32_t* utt_len,
+                                   int32_t n_split, float* scratch, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
