@@ -212,13 +212,18 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def i32_host(values) -> torch.Tensor:
+    """Row starts, lengths and the like (any iterable of integer-likes) as an int32 CPU tensor."""
+    return torch.tensor([int(v) for v in values], dtype=torch.int32)
+
+
 def plan_masked(lens, offsets, C: int, L: int, R: int, mask_lens=None):
     """Host planner (no GPU): returns (plan int32 CPU tensor, n_chunks list, out_lens list).
     lens: feature rows per utterance; mask_lens: xs_origin_lens when it differs (None = lens)."""
     B = len(lens)
-    lens_t = torch.tensor([int(x) for x in lens], dtype=torch.int32)
-    ml_t = torch.tensor([int(x) for x in mask_lens], dtype=torch.int32) if mask_lens is not None else None
-    offs_t = torch.tensor([int(x) for x in offsets], dtype=torch.int32) if offsets is not None else None
+    lens_t = i32_host(lens)
+    ml_t = i32_host(mask_lens) if mask_lens is not None else None
+    offs_t = i32_host(offsets) if offsets is not None else None
     nch = torch.zeros(B, dtype=torch.int32)
     olen = torch.zeros(B, dtype=torch.int32)
     total = I32(0)
@@ -244,7 +249,7 @@ def plan_stream(T: int, C: int, L: int, R: int, offset: int):
 
 def plan_padded(lens, T: int, C: int, L: int, R: int):
     B = len(lens)
-    lens_t = torch.tensor([int(x) for x in lens], dtype=torch.int32)
+    lens_t = i32_host(lens)
     tout = I32(0)
     n = I64(0)
     check(cfm_plan_padded(lens_t.data_ptr(), B, T, C, L, R, ctypes.byref(tout), None, ctypes.byref(n)))

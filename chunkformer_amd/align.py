@@ -218,9 +218,9 @@ def align_packed_device_raw(logp: torch.Tensor, row_start, row_len, targets: Seq
     flat = torch.tensor([v for t in tg for v in t] or [0], dtype=torch.int64)
     if int(flat.abs().max()) >= 1 << 31:
         raise ValueError("target ids must fit int32")
-    rl_h = torch.tensor([int(v) for v in row_len] or [0], dtype=torch.int32)
+    rl_h = _lib.i32_host(list(row_len) or [0])
     tl_h = torch.tensor(tl or [0], dtype=torch.int32)
-    rs_h = torch.tensor([int(v) for v in row_start] or [0], dtype=torch.int32)
+    rs_h = _lib.i32_host(list(row_start) or [0])
     ts_h = torch.tensor(tstart or [0], dtype=torch.int32)
     off_h = torch.zeros(max(B, 1), dtype=torch.int64)
     need = int(_lib.cfm_ctc_align_plan(rl_h.data_ptr(), tl_h.data_ptr(), B, off_h.data_ptr()))

@@ -61,8 +61,7 @@ def schema(c: ClassifierConfig) -> List[Tuple[str, Tuple[int, ...]]]:
 
 
 def _row_arrays(row_start, row_len, rows: int, device):
-    rs = torch.as_tensor([int(v) for v in row_start], dtype=torch.int32).reshape(-1)
-    rl = torch.as_tensor([int(v) for v in row_len], dtype=torch.int32).reshape(-1)
+    rs, rl = _lib.i32_host(row_start).reshape(-1), _lib.i32_host(row_len).reshape(-1)
     if rs.numel() != rl.numel():
         raise ValueError("row_start and row_len differ in length")
     if rs.numel() and (int((rs.long() + rl.long()).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):

@@ -15,13 +15,9 @@
 //   seg_scan_kernel      tile_off[s] = exclusive prefix sum of the segments' workgroup (16- or 64-query tile) counts
 //   aed_embed_kernel     x = embed[token] * sqrt(d) + pe[pos] (embedding.py:31-58), the right-to-left direction
 //                        reading the hypothesis' tokens in reverse by index; and the row's target id
-//   per block            LN1 -> Q, K|V GEMMs -> causal segment attention -> out GEMM (+= x)
-//                        LN2 -> Q GEMM, K|V GEMM over ALL memory rows of the batch (once per layer) -> cross
-//                        segment attention -> out GEMM (+= x);  LN3 -> w_1 + ReLU GEMM -> w_2 GEMM (+= x)
-//   after_norm, then in row slabs: output_layer GEMM -> aed_head_kernel: logit[target] - lse, one float per row
-//
-// GEMMs and LayerNorms are the library's launchers (gemm.hip, norm.hip) as they are; widths the LayerNorm launcher
-// does not take (d other than 128 / 256 / 512) use aed_ln_kernel, the same two-pass formula.
+//   the decoder blocks   aed_decoder_blocks (aed.h), with  self: K|V GEMM -> causal segment attention
+//                        cross: K|V GEMM over ALL memory rows of the batch (once per layer) -> cross segment attention
+//   then in row slabs: output_layer GEMM (vocab_logits) -> aed_head_kernel: logit[target] - lse, one float per row
 //
 // Segment attention (one kernel family for both uses): descriptor (Q0, NQ, K0, NK, CAUSAL): queries rows
 // [Q0, Q0 + NQ) of q, keys rows [K0, K0 + NK) of the K|V rows, query i sees keys j < NK (causal: j <= i);
@@ -30,11 +26,7 @@
 // binary search in tile_off (generic: one wave, 16 queries; mfma: four waves, 64 queries of one segment, sharing
 // each staged key tile).  Rows no descriptor covers are never read or written.
 //   generic   any type, dk a multiple of 16 up to 128: lane (query, quarter of the head's dims), keys one at a time
-//   mfma      bf16 / f16, dk 64 / 128: transposed, S^T = K . Q^T (keys on the MFMA row axis, queries on lanes) in
-//             32-key tiles, so a query's scores sit in one lane column (softmax reductions: 8 registers and two
-//             shuffles) and the probabilities are the B operand of O^T = V^T . P^T as they stand (their key order is
-//             a fixed permutation that the V^T fragment read matches); the K rows and V^T of a tile are staged
-//             through LDS once for the workgroup's four waves.
+//   mfma      bf16 / f16, dk 64 / 128: the 32-key tile of attn_core.h, staged once for the workgroup's four waves
 // Loops are bounded by the descriptor lengths; nothing waits on another workgroup; plain vector stores only.
 #include <hip/hip_runtime.h>
 
@@ -49,6 +41,7 @@
 #include "../../include/cfm.h"
 #include "../../include/cfm_ops.h"
 #include "aed.h"
+#include "attn_core.h"
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 #include "status.h"
@@ -121,8 +114,6 @@ CFM_DEV bool seg_find(const int32_t* __restrict__ desc, const int32_t* __restric
   nqt = min(TQ, g.nq - qi0);
   return nqt > 0;
 }
-
-template <typename T> struct Vec4 { typedef T type __attribute__((ext_vector_type(4))); };
 
 template <typename T, int DKQ>
 __global__ __launch_bounds__(64) void seg_attn_generic_kernel(const T* __restrict__ q, int ldq, const T* __restrict__ k,
@@ -198,11 +189,8 @@ __global__ __launch_bounds__(256) void seg_attn_mfma_kernel(const T* __restrict_
                                                             int k_rows, float scale) {
   typedef typename Vec4<T>::type V4;
   typedef typename Frag<T>::type F8;
-  constexpr int KS = DK / 32;   // 32-deep steps of Q . K^T
-  constexpr int NJ = DK / 16;   // 16-dim tiles of the output
-  constexpr int KP = DK + 8;    // K pitch in elements (144 / 272 B: conflict-free 16-row fragment reads)
-  constexpr int VP = 40;        // V^T pitch in elements (80 B: 8-B aligned 4-key reads)
-  constexpr int CH = DK / 8;    // 16-B chunks per row
+  typedef AttnTile<DK> G;   // the tile's geometry and key permutation: attn_core.h
+  constexpr int KS = G::KS, NJ = G::NJ, KP = G::KP, VP = G::VP, CH = G::CH;
   __shared__ __attribute__((aligned(16))) T ks[32 * KP];
   __shared__ __attribute__((aligned(16))) T vt[DK * VP];
   Seg g;
@@ -436,14 +424,10 @@ struct AedT : public cfm_aed {
     float *x, *logits;
     T *h, *q, *kv, *ao, *hid, *memT, *mkv;
   };
-  // rows of the output head's logit slab: at most 16384 rows and 512 MiB (as cfm_ctc_topk bounds its own)
-  int slab_rows() const {
-    const size_t r = (((size_t)512 << 20) / ((size_t)cfg.V * sizeof(float))) / 256 * 256;
-    return (int)std::min<size_t>(16384, std::max<size_t>(256, r));
-  }
+  int slab_rows() const { return logit_slab_rows(cfg.V); }   // rows of the output head's logit slab
   WS carve(void* base, int tokens, int mem_rows, size_t* total) const {
     const size_t d = cfg.d, ff = cfg.ff, n = (size_t)std::max(tokens, 1), mr = (size_t)std::max(mem_rows, 1);
-    AedCarver c(base);
+    Carver c(base);
     WS w;
     w.status = c.take<int32_t>(64);
     w.d_self = c.take<int32_t>(n * SD_INTS);
@@ -484,22 +468,17 @@ struct AedT : public cfm_aed {
                    const int32_t* tokens, int n_tok, const int32_t* hyp_start, const int32_t* hyp_len,
                    const int32_t* hyp_utt, int n_hyps, int dirs, float* out_l2r, float* out_r2l, void* ws, size_t wsb,
                    hipStream_t st) const override {
-    const int d = cfg.d, ff = cfg.ff, V = cfg.V;
+    const int d = cfg.d, V = cfg.V;
     if (wsb < ws_bytes(n_tok, mem_rows)) return set_error(CFM_ERR_VALUE, "attention decoder workspace too small");
     WS w = carve(ws, n_tok, mem_rows, nullptr);
     if (hipMemsetAsync(w.status, 0, 256, st) != hipSuccess) return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
     hipLaunchKernelGGL(aed_prepare_kernel, dim3(n_hyps), dim3(256), 0, st, tokens, n_tok, hyp_start, hyp_len, hyp_utt,
                        n_hyps, utt_start, utt_len, B, mem_rows, V, w.d_self, w.d_cross, w.status);
-    AED_KCHK((int)hipGetLastError());
+    KCHK((int)hipGetLastError());
     // one scan serves both attention uses: they share the query ranges
-    AED_KCHK(seg_scan(w.d_self, n_hyps, n_tok, n_tok, uses_mfma() ? SEG_MFMA_TQ : 16, w.tile_off, w.status, st));
+    KCHK(seg_scan(w.d_self, n_hyps, n_tok, n_tok, uses_mfma() ? SEG_MFMA_TQ : 16, w.tile_off, w.status, st));
     const T* memT;
-    if constexpr (sizeof(T) == 4) {
-      memT = mem;
-    } else {
-      AED_KCHK(att_cache_in<T>(mem, mem_rows, d, w.memT, st));   // f32 -> T rows
-      memT = w.memT;
-    }
+    KCHK(aed_memory_rows<T>(mem, mem_rows, d, w.memT, st, &memT));
     for (int dir = 0; dir < 2; ++dir) {
       if (!(dirs >> dir & 1)) continue;
       const AedDecoderW& D = dec[dir];
@@ -510,52 +489,27 @@ struct AedT : public cfm_aed {
         return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
       hipLaunchKernelGGL(aed_embed_kernel, dim3(n_hyps), dim3(256), 0, st, tokens, w.d_self, d, cfg.sos, cfg.eos, dir,
                          D.embed, pe, std::sqrt((float)d), w.x, w.target);
-      AED_KCHK((int)hipGetLastError());
-      for (const AedLayerW& L : D.layers) {
-        // x += SelfAttn(LN1(x)), causal inside each hypothesis
-        AED_KCHK(aed_layernorm<T>(w.x, n_tok, d, L.n1w, L.n1b, cfg.eps, w.h, st));
-        { EpiArgs e; e.bias = L.bq_s; e.out = w.q; e.ldo = d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wq_s, d, n_tok, d, d, e, st)); }
-        { EpiArgs e; e.bias = L.bkv_s; e.out = w.kv; e.ldo = 2 * d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wkv_s, d, n_tok, 2 * d, d, e, st)); }
-        AED_KCHK(attention(w.q, w.kv, w.ao, w.d_self, w.tile_off, n_hyps, n_tok, n_tok, st));
-        { EpiArgs e; e.bias = L.bo_s; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.ao, d, (const T*)L.wo_s, d, n_tok, d, d, e, st)); }
-        // x += SrcAttn(LN2(x), memory): K|V of every memory row of the batch in one GEMM
-        AED_KCHK(aed_layernorm<T>(w.x, n_tok, d, L.n2w, L.n2b, cfg.eps, w.h, st));
-        { EpiArgs e; e.bias = L.bq_c; e.out = w.q; e.ldo = d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wq_c, d, n_tok, d, d, e, st)); }
-        { EpiArgs e; e.bias = L.bkv_c; e.out = w.mkv; e.ldo = 2 * d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, memT, d, (const T*)L.wkv_c, d, mem_rows, 2 * d, d, e, st)); }
-        AED_KCHK(attention(w.q, w.mkv, w.ao, w.d_cross, w.tile_off, n_hyps, n_tok, mem_rows, st));
-        { EpiArgs e; e.bias = L.bo_c; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.ao, d, (const T*)L.wo_c, d, n_tok, d, d, e, st)); }
-        // x += W2 ReLU(W1 LN3(x))
-        AED_KCHK(aed_layernorm<T>(w.x, n_tok, d, L.n3w, L.n3b, cfg.eps, w.h, st));
-        { EpiArgs e; e.bias = L.b1; e.out = w.hid; e.ldo = ff;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_RELU, w.h, d, (const T*)L.w1, d, n_tok, ff, d, e, st)); }
-        { EpiArgs e; e.bias = L.b2; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.hid, ff, (const T*)L.w2, ff, n_tok, d, ff, e, st)); }
-      }
-      AED_KCHK(aed_layernorm<T>(w.x, n_tok, d, D.an_w, D.an_b, cfg.eps, w.h, st));
-      // output layer in row slabs: the vocabulary splits into a 256-multiple part (256 x 256 MFMA tiles) and a
-      // remainder, as the CTC head's GEMM does (model.hip head_logits)
-      const int slab = slab_rows();
-      const int V1 = (sizeof(T) == 2 && V % 4 == 0) ? V / 256 * 256 : 0;
+      KCHK((int)hipGetLastError());
+      // self: causal inside each hypothesis; cross: K|V of every memory row of the batch in one GEMM per block
+      KCHK(aed_decoder_blocks<T>(
+          D, cfg, n_tok, w.x, w.h, w.q, w.ao, w.hid,
+          [&](int, const AedLayerW& L, const T* h) {
+            EpiArgs e; e.bias = L.bkv_s; e.out = w.kv; e.ldo = 2 * d;
+            if (const int r = gemm<T>(EPI_STORE, ACT_NONE, h, d, (const T*)L.wkv_s, d, n_tok, 2 * d, d, e, st)) return r;
+            return attention(w.q, w.kv, w.ao, w.d_self, w.tile_off, n_hyps, n_tok, n_tok, st);
+          },
+          [&](int, const AedLayerW& L, const T* q) {
+            if (const int r = aed_memory_kv<T>(L, memT, mem_rows, d, w.mkv, st)) return r;
+            return attention(q, w.mkv, w.ao, w.d_cross, w.tile_off, n_hyps, n_tok, mem_rows, st);
+          },
+          st));
+      const int slab = slab_rows();   // output layer in row slabs
       for (int r0 = 0; r0 < n_tok; r0 += slab) {
         const int nr = std::min(slab, n_tok - r0);
-        const T* A = w.h + (size_t)r0 * d;
-        if (V1 > 0) {
-          EpiArgs e; e.bias = D.out_b; e.out = w.logits; e.ldo = V;
-          AED_KCHK(gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, (const T*)D.out_w, d, nr, V1, d, e, st));
-        }
-        if (V1 < V) {
-          EpiArgs e; e.bias = D.out_b + V1; e.out = w.logits + V1; e.ldo = V;
-          AED_KCHK(gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, (const T*)D.out_w + (size_t)V1 * d, d, nr, V - V1, d, e, st));
-        }
+        KCHK(vocab_logits<T>(w.h + (size_t)r0 * d, nr, (const T*)D.out_w, D.out_b, V, d, w.logits, V, st));
         hipLaunchKernelGGL(aed_head_kernel, dim3((nr + 3) / 4), dim3(256), 0, st, w.logits, nr, V, w.target + r0,
                            outp + r0);
-        AED_KCHK((int)hipGetLastError());
+        KCHK((int)hipGetLastError());
       }
     }
     return CFM_OK;
@@ -579,8 +533,8 @@ static cfm_status aed_build(const cfm_aed_config& cfg, const std::map<std::strin
   std::vector<char> img;
   std::vector<std::pair<size_t, void**>> fix;
   auto reserve = [&](size_t bytes) {
-    const size_t off = aed_align(img.size());
-    img.resize(off + aed_align(bytes));
+    const size_t off = align_up(img.size());
+    img.resize(off + align_up(bytes));
     return off;
   };
   auto get = [&](const std::string& k, int64_t numel) -> const float* {
@@ -759,7 +713,7 @@ cfm_status cfm_op_seg_attention(int32_t dtype, int32_t kernel, const void* q, in
   int32_t* status = scratch;
   int32_t* tile_off = scratch + 1;
   if (hipMemsetAsync(status, 0, 4, st) != hipSuccess) return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
-  AED_KCHK(seg_scan(desc, n_seg, q_rows, k_rows, kernel == CFM_SEG_ATTN_MFMA ? SEG_MFMA_TQ : 16, tile_off, status, st));
+  KCHK(seg_scan(desc, n_seg, q_rows, k_rows, kernel == CFM_SEG_ATTN_MFMA ? SEG_MFMA_TQ : 16, tile_off, status, st));
   int r = -1;
 #define SEG_CALL(FN, T_)                                                                                            \
   r = FN<T_>((const T_*)q, d, (const T_*)kv, (const T_*)kv + d, 2 * d, (T_*)out, d, desc, tile_off, n_seg, q_rows, \

@@ -7,10 +7,10 @@
 //
 //   attdec_init_kernel     validates the utterance row ranges and limits (status word), start state
 //   attdec_embed_kernel    x = embed[last token] * sqrt(d) + pe[i - 1]
-//   per block              LN1 -> Q GEMM, K|V GEMM written straight into the self-attention cache at (layer, i - 1, r)
-//                          -> attdec_self_kernel -> out GEMM (+= x);  LN2 -> Q GEMM -> attdec_cross_* (-> combine) ->
-//                          out GEMM (+= x);  LN3 -> w_1 + ReLU GEMM -> w_2 GEMM (+= x)
-//   after_norm, output_layer GEMM [R, V], ctc_topk_rows (logit - lse, top N, value descending / index ascending)
+//   the decoder blocks     aed_decoder_blocks (aed.h), with  self: K|V GEMM written straight into the self-attention
+//                          cache at (layer, i - 1, r) -> attdec_self_kernel;  cross: attdec_cross_* (-> combine) over
+//                          the memory K|V that begin projected
+//   output_layer GEMM [R, V] (vocab_logits), ctc_topk_rows (logit - lse, top N, value descending / index ascending)
 //   attdec_prune_kernel    one workgroup per utterance: finished-beam masking, top N of N * N, scores, tokens, end
 //                          flags, trace row, ancestry, freezing, the count of running utterances
 //   attdec_finish_kernel   backtrace through the trace, length penalty, selection
@@ -23,8 +23,7 @@
 // to 16 beams are the 16 query columns of one wave:
 //   generic   any type, head dim a multiple of 16 up to 128: lane (beam, quarter of the head's dims), keys one at a
 //             time, every key row read once for all beams
-//   mfma      bf16 / f16, head dim 64 / 128: S^T = K . Q^T and O^T = V^T . P^T on 32-key tiles, as the segment
-//             attention of aed.hip does, the beams on the lanes' column axis
+//   mfma      bf16 / f16, head dim 64 / 128: the 32-key tile of attn_core.h, the beams on the lanes' column axis
 // With more than one key split the parts write (m, l, unnormalised o) and attdec_combine_kernel merges them.
 // Loops are bounded by launch arguments and validated lengths; plain vector stores only.
 #include <hip/hip_runtime.h>
@@ -36,6 +35,7 @@
 #include "../../include/cfm.h"
 #include "../../include/cfm_ops.h"
 #include "aed.h"
+#include "attn_core.h"
 
 namespace cfm {
 
@@ -43,16 +43,6 @@ constexpr int ATTDEC_MAX_BEAM = 16;
 constexpr int ATTDEC_MAX_SPLIT = 16;
 enum { ADW_STATUS = 0, ADW_RUNNING = 1, ADW_INTS = 64 };
 enum { ATTDEC_ST_UTT = 2, ATTDEC_ST_LIMIT = 5 };
-
-// order-preserving float <-> uint32 (larger float = larger key), as ctc_beam.hip orders its values
-CFM_DEV uint32_t ad_f2key(float f) {
-  uint32_t u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-CFM_DEV float ad_key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-template <typename T> struct AdVec4 { typedef T type __attribute__((ext_vector_type(4))); };
 
 // ----------------------------------------------------------------------------- state kernels
 __global__ __launch_bounds__(64) void attdec_init_kernel(const int32_t* __restrict__ ustart_in,
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(64) void attdec_self_kernel(const T* __restrict__ q
                                                          const int32_t* __restrict__ anc, int anc_ld, int n_keys, int R,
                                                          int N, int d, const int32_t* __restrict__ done,
                                                          T* __restrict__ out, float scale) {
-  typedef typename AdVec4<T>::type V4;
+  typedef typename Vec4<T>::type V4;
   constexpr int DK = 4 * DKQ;
   const int r = blockIdx.x;
   if (done && done[r / N]) return;
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(64) void attdec_cross_generic_kernel(const T* __res
                                                                   const int32_t* __restrict__ done, int R, int N, int d,
                                                                   T* __restrict__ out, float* __restrict__ part_o,
                                                                   float* __restrict__ part_ml, float scale) {
-  typedef typename AdVec4<T>::type V4;
+  typedef typename Vec4<T>::type V4;
   constexpr int DK = 4 * DKQ;
   int k0, j0, j1;
   if (!ad_cross_range(ustart, ulen, done, mem_rows, k0, j0, j1)) return;
@@ -266,13 +256,10 @@ __global__ __launch_bounds__(64) void attdec_cross_mfma_kernel(const T* __restri
                                                                const int32_t* __restrict__ done, int R, int N, int d,
                                                                T* __restrict__ out, float* __restrict__ part_o,
                                                                float* __restrict__ part_ml, float scale) {
-  typedef typename AdVec4<T>::type V4;
+  typedef typename Vec4<T>::type V4;
   typedef typename Frag<T>::type F8;
-  constexpr int KS = DK / 32;   // 32-deep steps of Q . K^T
-  constexpr int NJ = DK / 16;   // 16-dim tiles of the output
-  constexpr int KP = DK + 8;    // K pitch in elements
-  constexpr int VP = 40;        // V^T pitch in elements
-  constexpr int CH = DK / 8;    // 16-B chunks per row
+  typedef AttnTile<DK> G;   // the tile's geometry and key permutation: attn_core.h
+  constexpr int KS = G::KS, NJ = G::NJ, KP = G::KP, VP = G::VP, CH = G::CH;
   __shared__ __attribute__((aligned(16))) T ks[32 * KP];
   __shared__ __attribute__((aligned(16))) T vt[DK * VP];
   int k0, j0, j1;
@@ -421,7 +408,7 @@ __global__ __launch_bounds__(256) void attdec_prune_kernel(int i, int N, int R, 
         const bool f = fin[row] != 0;
         const float sc = score[row];
         const float val = f ? (k == 0 ? sc : -INFINITY) : sc + tv[(size_t)row * N + k];
-        key[qd] = ad_f2key(val);
+        key[qd] = f2key(val);
         ctok[qd] = f ? eos : ti[(size_t)row * N + k];
       }
     }
@@ -454,7 +441,7 @@ __global__ __launch_bounds__(256) void attdec_prune_kernel(int i, int N, int R, 
       if (lane == 0) {
         s_par[r] = sel / N;
         s_tok[r] = tk;
-        s_val[r] = ad_key2f(bk);
+        s_val[r] = key2f(bk);
       }
     }
   }
@@ -615,7 +602,7 @@ struct AttDec {
   static WS carve(const cfm_aed* a, void* base, const AdGeom& g, size_t* total) {
     const size_t d = a->cfg.d, ff = a->cfg.ff, V = a->cfg.V, nb = a->dec[0].layers.size();
     const size_t B = std::max(g.B, 1), R = std::max(g.R, 1), S = std::max(g.S, 1), mr = std::max(g.mem_rows, 1);
-    AedCarver c(base);
+    Carver c(base);
     WS w;
     w.words = c.take<int32_t>(ADW_INTS);
     w.ustart = c.take<int32_t>(B);
@@ -655,27 +642,21 @@ struct AttDec {
     WS w = carve(a, ws, g, nullptr);
     const size_t tr = (size_t)std::max(g.S, 1) * std::max(g.R, 1);
     if (hipMemsetAsync(w.words, 0, w.zero_bytes, st) != hipSuccess ||
-        hipMemsetAsync(w.tr_parent, 0xff, aed_align(tr * 4), st) != hipSuccess ||
-        hipMemsetAsync(w.tr_token, 0xff, aed_align(tr * 4), st) != hipSuccess ||
-        hipMemsetAsync(w.tr_score, 0, aed_align(tr * 4), st) != hipSuccess ||
+        hipMemsetAsync(w.tr_parent, 0xff, align_up(tr * 4), st) != hipSuccess ||
+        hipMemsetAsync(w.tr_token, 0xff, align_up(tr * 4), st) != hipSuccess ||
+        hipMemsetAsync(w.tr_score, 0, align_up(tr * 4), st) != hipSuccess ||
         hipMemsetAsync(w.ao, 0, (size_t)g.R * d * sizeof(T), st) != hipSuccess)
       return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
     hipLaunchKernelGGL(attdec_init_kernel, dim3(g.B), dim3(64), 0, st, ustart, ulen, limit, g.B, g.N, g.mem_rows, g.S,
                        a->cfg.sos, w.words, w.ustart, w.ulen, w.limit, w.done, w.tok, w.score);
-    AED_KCHK((int)hipGetLastError());
+    KCHK((int)hipGetLastError());
     if (g.mem_rows > 0) {
       const T* memT;
-      if constexpr (sizeof(T) == 4) {
-        memT = mem;
-      } else {
-        AED_KCHK(att_cache_in<T>(mem, g.mem_rows, d, w.memT, st));   // f32 -> T rows
-        memT = w.memT;
-      }
+      KCHK(aed_memory_rows<T>(mem, g.mem_rows, d, w.memT, st, &memT));
       // cross-attention K|V of every left-decoder block, once, over all encoder rows of the batch
       size_t l = 0;
       for (const AedLayerW& L : a->dec[0].layers) {
-        EpiArgs e; e.bias = L.bkv_c; e.out = w.mkv + l * (size_t)g.mem_rows * 2 * d; e.ldo = 2 * d;
-        AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, memT, d, (const T*)L.wkv_c, d, g.mem_rows, 2 * d, d, e, st));
+        KCHK(aed_memory_kv<T>(L, memT, g.mem_rows, d, w.mkv + l * (size_t)g.mem_rows * 2 * d, st));
         ++l;
       }
     }
@@ -683,8 +664,7 @@ struct AttDec {
   }
 
   static cfm_status steps(const cfm_aed* a, const AdGeom& g, int step0, int n_steps, void* ws, hipStream_t st) {
-    const int d = a->cfg.d, ff = a->cfg.ff, V = a->cfg.V, H = a->cfg.H, dk = d / H, R = g.R, N = g.N, S = g.S;
-    const float eps = a->cfg.eps;
+    const int d = a->cfg.d, V = a->cfg.V, H = a->cfg.H, dk = d / H, R = g.R, N = g.N, S = g.S;
     WS w = carve(a, ws, g, nullptr);
     const AedDecoderW& D = a->dec[0];
     const int ck = cross_mfma(a) ? AD_KERNEL_CROSS_MFMA : AD_KERNEL_CROSS_GENERIC;
@@ -693,53 +673,30 @@ struct AttDec {
       int32_t* anc_nxt = w.anc + (size_t)(i & 1) * R * S;
       hipLaunchKernelGGL(attdec_embed_kernel, dim3(R), dim3(128), 0, st, w.tok, d, i - 1, D.embed, a->pe,
                          std::sqrt((float)d), w.x);
-      AED_KCHK((int)hipGetLastError());
-      size_t l = 0;
-      for (const AedLayerW& L : D.layers) {
-        T* kvl = w.kvc + l * (size_t)S * R * 2 * d;
-        // x += SelfAttn(LN1(x)): this step's K|V row goes to (layer, position i - 1, slot r) and stays there
-        AED_KCHK(aed_layernorm<T>(w.x, R, d, L.n1w, L.n1b, eps, w.h, st));
-        { EpiArgs e; e.bias = L.bq_s; e.out = w.q; e.ldo = d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wq_s, d, R, d, d, e, st)); }
-        { EpiArgs e; e.bias = L.bkv_s; e.out = kvl + (size_t)(i - 1) * R * 2 * d; e.ldo = 2 * d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wkv_s, d, R, 2 * d, d, e, st)); }
-        { const int r = ad_self_attention<T>(w.q, kvl, anc_cur, S, i, R, N, H, dk, w.done, w.ao, st);
-          AED_KCHK(r == -1 ? (int)hipErrorInvalidValue : r); }
-        { EpiArgs e; e.bias = L.bo_s; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.ao, d, (const T*)L.wo_s, d, R, d, d, e, st)); }
-        // x += SrcAttn(LN2(x), memory): the utterance's projected rows, shared by its beams
-        AED_KCHK(aed_layernorm<T>(w.x, R, d, L.n2w, L.n2b, eps, w.h, st));
-        { EpiArgs e; e.bias = L.bq_c; e.out = w.q; e.ldo = d;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_NONE, w.h, d, (const T*)L.wq_c, d, R, d, d, e, st)); }
-        { const int r = ad_cross_attention<T>(ck, w.q, w.mkv + l * (size_t)g.mem_rows * 2 * d, g.mem_rows, w.ustart,
-                                              w.ulen, w.done, g.B, N, H, dk, g.ns, w.ao, w.part_o, w.part_ml, st);
-          AED_KCHK(r == -1 ? (int)hipErrorInvalidValue : r); }
-        { EpiArgs e; e.bias = L.bo_c; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.ao, d, (const T*)L.wo_c, d, R, d, d, e, st)); }
-        // x += W2 ReLU(W1 LN3(x))
-        AED_KCHK(aed_layernorm<T>(w.x, R, d, L.n3w, L.n3b, eps, w.h, st));
-        { EpiArgs e; e.bias = L.b1; e.out = w.hid; e.ldo = ff;
-          AED_KCHK(gemm<T>(EPI_STORE, ACT_RELU, w.h, d, (const T*)L.w1, d, R, ff, d, e, st)); }
-        { EpiArgs e; e.bias = L.b2; e.x = w.x; e.ldx = d;
-          AED_KCHK(gemm<T>(EPI_RESID, ACT_NONE, w.hid, ff, (const T*)L.w2, ff, R, d, ff, e, st)); }
-        ++l;
-      }
-      AED_KCHK(aed_layernorm<T>(w.x, R, d, D.an_w, D.an_b, eps, w.h, st));
-      // output layer: a 256-multiple part and a remainder, as cfm_aed_score splits it
-      const int V1 = (sizeof(T) == 2 && V % 4 == 0) ? V / 256 * 256 : 0;
-      if (V1 > 0) {
-        EpiArgs e; e.bias = D.out_b; e.out = w.logits; e.ldo = V;
-        AED_KCHK(gemm<T>(EPI_STORE_F32, ACT_NONE, w.h, d, (const T*)D.out_w, d, R, V1, d, e, st));
-      }
-      if (V1 < V) {
-        EpiArgs e; e.bias = D.out_b + V1; e.out = w.logits + V1; e.ldo = V;
-        AED_KCHK(gemm<T>(EPI_STORE_F32, ACT_NONE, w.h, d, (const T*)D.out_w + (size_t)V1 * d, d, R, V - V1, d, e, st));
-      }
-      AED_KCHK(ctc_topk_rows(w.logits, R, V, N, 1, w.tv, w.ti, st));
+      KCHK((int)hipGetLastError());
+      // self: this step's K|V row goes to (layer, position i - 1, slot r) and stays there; cross: the utterance's
+      // rows as begin projected them, shared by its beams
+      KCHK(aed_decoder_blocks<T>(
+          D, a->cfg, R, w.x, w.h, w.q, w.ao, w.hid,
+          [&](int l, const AedLayerW& L, const T* h) {
+            T* kvl = w.kvc + (size_t)l * S * R * 2 * d;
+            EpiArgs e; e.bias = L.bkv_s; e.out = kvl + (size_t)(i - 1) * R * 2 * d; e.ldo = 2 * d;
+            if (const int r = gemm<T>(EPI_STORE, ACT_NONE, h, d, (const T*)L.wkv_s, d, R, 2 * d, d, e, st)) return r;
+            const int r = ad_self_attention<T>(w.q, kvl, anc_cur, S, i, R, N, H, dk, w.done, w.ao, st);
+            return r == -1 ? (int)hipErrorInvalidValue : r;
+          },
+          [&](int l, const AedLayerW&, const T* q) {
+            const int r = ad_cross_attention<T>(ck, q, w.mkv + (size_t)l * g.mem_rows * 2 * d, g.mem_rows, w.ustart,
+                                                w.ulen, w.done, g.B, N, H, dk, g.ns, w.ao, w.part_o, w.part_ml, st);
+            return r == -1 ? (int)hipErrorInvalidValue : r;
+          },
+          st));
+      KCHK(vocab_logits<T>(w.h, R, (const T*)D.out_w, D.out_b, V, d, w.logits, V, st));
+      KCHK(ctc_topk_rows(w.logits, R, V, N, 1, w.tv, w.ti, st));
       hipLaunchKernelGGL(attdec_prune_kernel, dim3(g.B), dim3(256), 0, st, i, N, R, S, a->cfg.eos, w.tv, w.ti, w.score,
                          w.tok, w.fin, anc_cur, anc_nxt, w.tr_parent, w.tr_token, w.tr_score, w.limit, w.done, w.steps,
                          w.words);
-      AED_KCHK((int)hipGetLastError());
+      KCHK((int)hipGetLastError());
     }
     return CFM_OK;
   }
@@ -750,7 +707,7 @@ struct AttDec {
     WS w = carve(a, ws, g, nullptr);
     hipLaunchKernelGGL(attdec_finish_kernel, dim3(g.B), dim3(64), 0, st, g.N, g.R, g.S, a->cfg.sos, a->cfg.eos, penalty,
                        w.score, w.steps, w.tr_parent, w.tr_token, tokens, lens, final_scores, best);
-    AED_KCHK((int)hipGetLastError());
+    KCHK((int)hipGetLastError());
     const size_t tr = (size_t)g.S * g.R * 4;
     if (tr_parent && tr_token && tr_score && tr > 0) {
       if (hipMemcpyAsync(tr_parent, w.tr_parent, tr, hipMemcpyDeviceToDevice, st) != hipSuccess ||

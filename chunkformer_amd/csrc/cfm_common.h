@@ -40,6 +40,7 @@ template <typename T> struct Frag;
 template <> struct Frag<float> { typedef f32x8 type; };
 template <> struct Frag<bf16> { typedef bf16x8 type; };
 template <> struct Frag<f16> { typedef f16x8 type; };
+template <typename T> struct Vec4 { typedef T type __attribute__((ext_vector_type(4))); };
 
 CFM_DEV float to_f32(float x) { return x; }
 CFM_DEV float to_f32(bf16 x) { return (float)x; }
@@ -180,6 +181,14 @@ CFM_DEV void lds_store_4bf16_a2(unsigned addr, unsigned lo, unsigned hi) {
       "v"(lo), "v"(hi)
       : "memory");
 }
+
+// order-preserving float <-> uint32 (larger float = larger key); -0 is keyed as +0, which it equals
+CFM_DEV uint32_t f2key(float f) {
+  uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+CFM_DEV float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 CFM_DEV float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 CFM_DEV float sigmoid_f(float x) { return 1.0f / (1.0f + __expf(-x)); }

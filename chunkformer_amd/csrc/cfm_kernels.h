@@ -88,6 +88,30 @@ template <typename T>
 int gemm(int epi, int act, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const EpiArgs& ep,
          hipStream_t st);
 
+// A vocabulary projection (the CTC head, the attention decoders' output layer): out[rows, V] f32 (row pitch ldo) =
+// A[rows, d] . W[V, d]^T + bias.  The vocabulary splits into a 256-multiple part (256 x 256 MFMA tiles) and a
+// remainder (128 x 128 tiles); f32x4 epilogue stores need the row pitch V % 4 == 0.  `tuned`: the caller's kernel
+// selection, if it has one.
+template <typename T>
+inline int vocab_logits(const T* A, int rows, const T* W, const float* bias, int V, int d, float* out, int ldo,
+                        hipStream_t st, const EpiArgs& tuned = EpiArgs()) {
+  const int V1 = (sizeof(T) == 2 && V % 4 == 0) ? V / 256 * 256 : 0;
+  if (V1 > 0) {
+    EpiArgs e = tuned; e.bias = bias; e.out = out; e.ldo = ldo;
+    if (const int r = gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, W, d, rows, V1, d, e, st)) return r;
+  }
+  if (V1 < V) {
+    EpiArgs e = tuned; e.bias = bias + V1; e.out = out + V1; e.ldo = ldo;
+    if (const int r = gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, W + (size_t)V1 * d, d, rows, V - V1, d, e, st)) return r;
+  }
+  return 0;
+}
+// rows of a logit slab [rows, V] f32 that bounds a workspace: at most 16384 rows (64 row tiles of 256: V = 5000 gives
+// 1280 head-GEMM tiles, five full rounds of 256 CUs) and at most 512 MiB, at least 256 rows; V > 0
+inline int logit_slab_rows(int V) {
+  const size_t r = (((size_t)512 << 20) / ((size_t)V * sizeof(float))) / 256 * 256;
+  return (int)(r < 256 ? 256 : r > 16384 ? 16384 : r);
+}
 
 // LayerNorm over d (eps) of f32 rows -> T rows; optional 0/1 row mask on the output.
 // fused residual add of the previous sub-block: x += alpha * ymask[row] * y (y null = none)

@@ -32,7 +32,9 @@
 #include <vector>
 
 #include "../../include/cfm.h"
+#include "cfm_common.h"
 #include "status.h"
+#include "workspace.h"
 
 namespace cfm {
 
@@ -149,12 +151,6 @@ __global__ __launch_bounds__(CLS_THREADS) void cls_slab_kernel(const float* __re
   if (active && g == 0) reinterpret_cast<float4*>(partial + (size_t)j * d)[c] = tot;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(CLS_THREADS) void cls_finish_kernel(int rows, int d, const int* __restrict__ row_start,
                                                                  const int* __restrict__ row_len,
                                                                  const int* __restrict__ slab_off,
@@ -233,7 +229,6 @@ __global__ __launch_bounds__(CLS_THREADS) void cls_finish_kernel(int rows, int d
   }
 }
 
-static size_t cls_align(size_t v) { return (v + 255) / 256 * 256; }
 static int cls_slab_cap(int rows, int B) { return (rows + CLS_SLAB - 1) / CLS_SLAB + B; }
 
 static cfm_status cls_run(const float* enc, int rows, int d, const int* row_start, const int* row_len, int B,
@@ -250,7 +245,7 @@ static cfm_status cls_run(const float* enc, int rows, int d, const int* row_star
     return set_error(CFM_ERR_VALUE, "enc / pooled / workspace must be 16-byte aligned");
   const int cap = cls_slab_cap(rows, B);
   int* slab_off = static_cast<int*>(ws);
-  float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + cls_align((size_t)(B + 1) * 4));
+  float* partial = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)(B + 1) * 4));
   hipLaunchKernelGGL(cls_scan_kernel, dim3(1), dim3(CLS_THREADS), 0, st, row_start, row_len, B, rows, cap, slab_off);
   hipLaunchKernelGGL(cls_slab_kernel, dim3(cap), dim3(CLS_THREADS), 0, st, enc, rows, d, row_start, row_len, B, slab_off,
                      partial);
@@ -324,7 +319,7 @@ void cfm_cls_destroy(cfm_cls* h) { delete h; }
 
 size_t cfm_cls_pool_workspace_bytes(int32_t rows, int32_t d, int32_t B) {
   if (rows < 0 || B < 0 || d < 0) return 0;
-  return cls_align((size_t)(B + 1) * 4) + cls_align((size_t)cls_slab_cap(rows, B) * d * 4);
+  return align_up((size_t)(B + 1) * 4) + align_up((size_t)cls_slab_cap(rows, B) * d * 4);
 }
 
 size_t cfm_cls_workspace_bytes(const cfm_cls* h, int32_t rows, int32_t B) {

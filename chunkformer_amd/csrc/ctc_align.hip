@@ -29,6 +29,7 @@
 #include "../../include/cfm.h"
 #include "cfm_common.h"
 #include "status.h"
+#include "workspace.h"
 
 namespace cfm {
 
@@ -50,7 +51,6 @@ struct AlignArgs {
   int rows, V, blank, n_targets, lds_states, lds_bytes;
 };
 
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 __host__ __device__ inline int64_t al_runs(int64_t L) { return (2 * L + 1 + 15) / 16; }
 __host__ __device__ inline size_t al_trellis_bytes(int64_t T, int64_t runs) {
   return ((size_t)T * (size_t)runs * 4 + 255) / 256 * 256;
@@ -353,7 +353,7 @@ using namespace cfm;
 size_t cfm_ctc_align_plan(const int32_t* row_len_host, const int32_t* target_len_host, int32_t B,
                           int64_t* ws_offset_host_out) {
   if (B < 0 || (B > 0 && (!row_len_host || !target_len_host))) return 0;
-  size_t at = up256((size_t)(B > 0 ? B : 1) * 4);
+  size_t at = align_up((size_t)(B > 0 ? B : 1) * 4);
   for (int b = 0; b < B; ++b) {
     const int64_t T = row_len_host[b] > 0 ? row_len_host[b] : 0, L = target_len_host[b] > 0 ? target_len_host[b] : 0;
     if (ws_offset_host_out) ws_offset_host_out[b] = (int64_t)at;
@@ -386,7 +386,7 @@ cfm_status cfm_ctc_align(const float* logp, int32_t rows, int32_t V, const int32
   a.lp = logp; a.row_start = row_start; a.row_len = row_len; a.targets = targets; a.target_start = target_start;
   a.target_len = target_len; a.ws_off = ws_offset; a.frames = frames; a.spans = spans; a.status = status;
   a.end_state = (int32_t*)ws; a.frame_logp = frame_logp; a.score = score; a.ws = (char*)ws; a.ws_bytes = wsb;
-  a.header_bytes = up256((size_t)B * 4); a.rows = rows; a.V = V; a.blank = blank_id; a.n_targets = n_targets;
+  a.header_bytes = align_up((size_t)B * 4); a.rows = rows; a.V = V; a.blank = blank_id; a.n_targets = n_targets;
   a.lds_states = lds_max_states < 0 || lds_max_states > AL_LDS_STATES ? AL_LDS_STATES : lds_max_states;
   const int64_t lds_runs = std::min<int64_t>(max_runs, (a.lds_states + 15) / 16);
   a.lds_bytes = AL_LDS_HEAD + (a.lds_states > 0 ? (int)(2 * al_row_bytes(lds_runs)) : 0);

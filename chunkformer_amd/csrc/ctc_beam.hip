@@ -33,18 +33,11 @@
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 #include "status.h"
+#include "workspace.h"
 
 namespace cfm {
 
 // ----------------------------------------------------------------------------- top-k
-// order-preserving float <-> uint32 (larger float = larger key); -0 is keyed as +0, which it equals
-CFM_DEV uint32_t f2key(float f) {
-  uint32_t u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-CFM_DEV float key2f(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 // One wave per row.  NPL > 0: the row in NPL registers per lane (V <= 64 * NPL), read once; NPL == 0: every
 // pass re-reads the row.  lse is formed exactly as log_softmax_kernel (misc.hip) forms it, and the
 // selection orders the VALUES written (logit - lse: two logits can round to one log-prob, and then the
@@ -479,7 +472,6 @@ struct cfm_ctx {
   CtxTables t{};
 };
 
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 cfm_status cfm_ctx_create(int32_t n_nodes, const int32_t* fail, const double* token_score, const double* node_score,
                           const double* output_score, int32_t n_trans, const int32_t* trans_node,
@@ -499,8 +491,8 @@ cfm_status cfm_ctx_create(int32_t n_nodes, const int32_t* fail, const double* to
     if (fail[i] < 0 || fail[i] >= n_nodes) return set_error(CFM_ERR_VALUE, "context graph: bad fail arc");
     off[i + 1] += off[i];
   }
-  const size_t nI = up256((size_t)n_nodes * 4), nO = up256((size_t)(n_nodes + 1) * 4), nT = up256((size_t)n_trans * 4 + 4),
-               nD = up256((size_t)n_nodes * 8);
+  const size_t nI = align_up((size_t)n_nodes * 4), nO = align_up((size_t)(n_nodes + 1) * 4),
+               nT = align_up((size_t)n_trans * 4 + 4), nD = align_up((size_t)n_nodes * 8);
   const size_t total = nI + nO + 2 * nT + 3 * nD;
   std::vector<char> img(total, 0);
   size_t o = 0;
@@ -548,8 +540,8 @@ size_t cfm_ctc_beam_workspace_bytes(int32_t rows, int32_t B, int32_t k, int32_t 
   (void)B;
   (void)n_context_nodes;   // the context tables live in the cfm_ctx handle
   if (rows < 0 || k < 1) return 0;
-  const size_t u = up256((size_t)k * (size_t)rows * 4);
-  return 256 + 2 * u + up256((size_t)2 * k * (size_t)rows * 4) + (with_times ? 2 * u : 0);
+  const size_t u = align_up((size_t)k * (size_t)rows * 4);
+  return 256 + 2 * u + align_up((size_t)2 * k * (size_t)rows * 4) + (with_times ? 2 * u : 0);
 }
 
 cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, int32_t rows, int32_t k,
@@ -574,12 +566,12 @@ cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, 
   a.rows = rows; a.k = k; a.blank = blank_id; a.has_ctx = context != nullptr; a.with_times = with_times;
   if (context) a.ctx = context->t;
   a.out_tok = out_tokens; a.out_time = out_times; a.out_len = out_len; a.out_score = out_score; a.n_hyps = n_hyps;
-  const size_t u = up256((size_t)k * (size_t)rows * 4);
+  const size_t u = align_up((size_t)k * (size_t)rows * 4);
   char* p = (char*)ws;
   a.err = (int32_t*)p; p += 256;
   a.node_par = (int32_t*)p; p += u;
   a.node_tok = (int32_t*)p; p += u;
-  a.map = (int32_t*)p; p += up256((size_t)2 * k * (size_t)rows * 4);
+  a.map = (int32_t*)p; p += align_up((size_t)2 * k * (size_t)rows * 4);
   if (with_times) { a.tprev = (int32_t*)p; p += u; a.tframe = (int32_t*)p; }
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(ws, 0, 256, st);

@@ -22,6 +22,7 @@
 #include "cfm_kernels.h"
 #include "plan.h"
 #include "status.h"
+#include "workspace.h"
 
 namespace cfm {
 
@@ -36,11 +37,6 @@ cfm_status set_error(cfm_status s, const std::string& msg) {
     hipError_t _e = (x);                                                                      \
     if (_e != hipSuccess) return set_error(CFM_ERR_RUNTIME, std::string(#x ": ") + hipGetErrorString(_e)); \
   } while (0)
-#define KCHK(x)                                                                               \
-  do {                                                                                        \
-    int _e = (x);                                                                             \
-    if (_e) return set_error(CFM_ERR_RUNTIME, std::string(#x ": ") + hipGetErrorString((hipError_t)_e)); \
-  } while (0)
 
 // time one launch (class CLS) with events when that class is enabled in prof_mask
 #define PROF(CLS, X)                      \
@@ -50,19 +46,6 @@ cfm_status set_error(cfm_status s, const std::string& msg) {
     KCHK(X);                              \
     prof_end(CLS, st, _pb);               \
   } while (0)
-
-static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename U> U* take(size_t n) {
-    U* p = (U*)(base ? base + off : nullptr);
-    off += align_up(n * sizeof(U));
-    return p;
-  }
-};
 
 struct LayerW {
   void *ff1m, *ff2m, *ff1, *ff2, *qkv, *pos, *wo, *pw1, *pw2;   // T matrices [N][K]
@@ -522,27 +505,13 @@ struct ModelT : public cfm_model {
     }
     float* dst = logp ? logp : logits;
     *out = dst;
-    // the vocabulary splits into a 256-multiple part (256 x 256 MFMA tiles) and a remainder (128 x 128
-    // tiles); f32x4 epilogue stores need the row pitch V % 4 == 0
-    const int V1 = (sizeof(T) == 2 && V % 4 == 0) ? V / 256 * 256 : 0;
-    if (V1 > 0) {
-      EpiArgs e = E(); e.bias = fe.ctc_b; e.out = dst; e.ldo = V;
-      PROF(PC_CTC, gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, (const T*)fe.ctc_w, d, rows, V1, d, e, st));
-    }
-    if (V1 < V) {
-      EpiArgs e = E(); e.bias = fe.ctc_b + V1; e.out = dst + V1; e.ldo = V;
-      PROF(PC_CTC, gemm<T>(EPI_STORE_F32, ACT_NONE, A, d, (const T*)fe.ctc_w + (size_t)V1 * d, d, rows, V - V1, d, e, st));
-    }
+    PROF(PC_CTC, vocab_logits<T>(A, rows, (const T*)fe.ctc_w, fe.ctc_b, V, d, dst, V, st, E()));
     return CFM_OK;
   }
 
   // per-frame top-k of the CTC log-probs (cfm_ctc_topk): row slabs bound the logit workspace
   int topk_slab_rows() const override {
-    if (cfg.vocab <= 0) return 0;
-    // at most 16384 rows (64 row tiles of 256: V = 5000 gives 1280 head-GEMM tiles, five full rounds of
-    // 256 CUs) and at most 512 MiB of logits
-    const size_t r = (((size_t)512 << 20) / ((size_t)cfg.vocab * sizeof(float))) / 256 * 256;
-    return (int)std::min<size_t>(16384, std::max<size_t>(256, r));
+    return cfg.vocab <= 0 ? 0 : logit_slab_rows(cfg.vocab);
   }
   size_t ctc_topk_ws_bytes(int rows) const override { return ctc_ws_bytes(std::min(rows, topk_slab_rows())); }
   cfm_status ctc_topk(const float* enc, int rows, int k, float* vals, int32_t* ids, void* ws, size_t wsb,

@@ -503,8 +503,7 @@ class ChunkFormerEncoder:
         dev = self.device
         ids = ids.reshape(-1).to(dev, torch.int32).contiguous()
         rows = ids.numel()
-        rs = torch.tensor([int(v) for v in row_start], dtype=torch.int32)
-        rl = torch.tensor([int(v) for v in row_len], dtype=torch.int32)
+        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
         if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
             raise ValueError("utterance row ranges exceed the id tensor")
         seg_mode = max_silence is not None

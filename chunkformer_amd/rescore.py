@@ -386,8 +386,7 @@ class AttentionRescorer:
             _check_hyps(c, nbest)
         enc = enc_rows.reshape(-1, c.d_model).to(dev, torch.float32).contiguous()
         rows, B = enc.shape[0], len(nbest)
-        rs = torch.tensor([int(v) for v in row_start], dtype=torch.int32)
-        rl = torch.tensor([int(v) for v in row_len], dtype=torch.int32)
+        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
         if check_host and B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
             raise ValueError("utterance row ranges exceed the encoder rows")
         right = bool(right) and c.has_right

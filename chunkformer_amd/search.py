@@ -405,8 +405,7 @@ def beam_search_topk_device(topk_logp: torch.Tensor, topk_ids: torch.Tensor, row
     vals = topk_logp.to(torch.float32).contiguous()
     ids = topk_ids.to(torch.int32).contiguous()
     rows, B = vals.shape[0], len(row_start)
-    rs = torch.tensor([int(v) for v in row_start], dtype=torch.int32)
-    rl = torch.tensor([int(v) for v in row_len], dtype=torch.int32)
+    rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
     if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
         raise ValueError("utterance row ranges exceed the top-k arrays")
     if B == 0:

@@ -232,8 +232,7 @@ class RNNTGreedy:
         enc = enc.reshape(-1, self.cfg.enc_dim).to(self.device, torch.float32).contiguous()
         rows = enc.shape[0]
         B = len(row_start)
-        rs = torch.tensor([int(v) for v in row_start], dtype=torch.int32)
-        rl = torch.tensor([int(v) for v in row_len], dtype=torch.int32)
+        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
         if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
             raise ValueError("utterance row ranges exceed the encoder rows")
         if n_steps < 1:

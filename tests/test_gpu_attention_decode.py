@@ -70,6 +70,33 @@ def test_fp32_matches_the_fixture(A, name):
     print(f"attention fp32 {name}: {len(m['cases'])} cases, worst score error {worst:.3f} of its bar (i x {BAR})")
 
 
+@pytest.mark.parametrize("name", ["d64h4", "d128h2"])   # head dim 16 (the generic kernels) and 64
+def test_search_score_equals_rescoring_of_its_own_hypothesis(A, name):
+    """Both consumers of the decoder run the same blocks: where the device's best hypothesis ends with eos, the
+    search's un-normalised score of it is the sum of AttentionRescorer.score's left-to-right log-probs of the same
+    tokens.  Each side is held to (steps + 1) x BAR of float64 by the tests above, so the two agree within twice that."""
+    m = fx.load_models()[name]
+    n_cases, worst = 0, 0.0
+    for c in m["cases"]:
+        dec = _decoder(A, name, c["recipe"], "fp32")
+        r = _device(A, name, c, "fp32")
+        row = r.beam_rows[r.best_index] if r.steps else []
+        if not row or row[-1] != m["cfg"].eos:
+            continue
+        n_cases += 1
+        searched = r.trace[-1][2][r.best_index]
+        l2r = dec.rescorer.score(c["enc"], [0], [c["enc"].shape[0]], [[r.tokens]], right=False)[0][0][0]
+        rescored = math.fsum(float(v) for v in l2r.tolist())
+        bar = 2 * (r.steps + 1) * BAR
+        print(f"attention fp32 {name}: steps {r.steps}, search {searched:.6f}, rescoring {rescored:.6f}, "
+              f"|difference| {abs(searched - rescored) / bar:.3f} of its bar")
+        assert abs(searched - rescored) <= bar, (searched, rescored, bar)
+        worst = max(worst, abs(searched - rescored) / bar)
+    print(f"attention fp32 {name}: search score vs rescoring on {n_cases} cases, worst {worst:.3f} of "
+          f"2 (steps + 1) x {BAR}")
+    assert n_cases >= 1, "no fixture case whose best hypothesis ends with eos"
+
+
 def _compare_until_open(dev, host):
     """-> (steps compared, compared to the end).  Equal parents / tokens and scores within i x BAR up to the first
     step the host's own gap leaves open."""
