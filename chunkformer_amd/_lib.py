@@ -120,6 +120,12 @@ CFM_RNNT_ONE_WORKGROUP = 1
 cfm_rnnt_set_option = _sig("cfm_rnnt_set_option", I32, P, ctypes.c_char_p, I64)
 cfm_rnnt_grid_blocks = _sig("cfm_rnnt_grid_blocks", I32, P, I32)
 cfm_rnnt_error = _sig("cfm_rnnt_error", I32, P, P, I32)
+# transducer prefix beam search over the same handle (csrc/rnnt_beam.hip)
+F32 = ctypes.c_float
+cfm_rnnt_beam_workspace_bytes = _sig("cfm_rnnt_beam_workspace_bytes", SZ, P, I32, I32, I32)
+cfm_rnnt_beam_search = _sig("cfm_rnnt_beam_search", I32, P, P, I32, P, P, P, I32, I32, I32, F32, F32, P, P, P, P, P, P, P,
+                            P, P, P, P, SZ, P)
+cfm_rnnt_beam_error = _sig("cfm_rnnt_beam_error", I32, P)
 # classification consumer (include/cfm.h)
 CLS_MAX_TASKS = 16
 
@@ -162,7 +168,14 @@ cfm_op_gemm = _sig("cfm_op_gemm", I32, I32, I32, I32, P, I32, P, I32, I32, I32, 
 ATTN_GENERIC, ATTN_RING, ATTN_A128, ATTN_DENSE = 0, 1, 2, 3
 cfm_op_attention = _sig("cfm_op_attention", I32, I32, I32, P, P, I32, P, I32, I32, P, P, P, I32, I32, I32, I32, I32, P,
                         I32, P, I32, I32, I32, I32, P)
-EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_seg_attention", "cfm_op_decode_attention"]
+cfm_op_rnnt_fused_topk = _sig("cfm_op_rnnt_fused_topk", I32, P, P, I32, I32, I32, F32, F32, P, P, P)
+cfm_op_rnnt_beam_prune_workspace_bytes = _sig("cfm_op_rnnt_beam_prune_workspace_bytes", SZ, I32, I32)
+cfm_op_rnnt_beam_prune = _sig("cfm_op_rnnt_beam_prune", I32, P, P, I32, I32, I32, P, P, P, P, P, SZ, P)
+cfm_op_rnnt_lstm_step_workspace_bytes = _sig("cfm_op_rnnt_lstm_step_workspace_bytes", SZ, P, I32)
+cfm_op_rnnt_lstm_step = _sig("cfm_op_rnnt_lstm_step", I32, P, P, P, P, I32, P, P, P, P, SZ, P)
+EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_seg_attention", "cfm_op_decode_attention",
+                "cfm_op_rnnt_fused_topk", "cfm_op_rnnt_beam_prune_workspace_bytes", "cfm_op_rnnt_beam_prune",
+                "cfm_op_rnnt_lstm_step_workspace_bytes", "cfm_op_rnnt_lstm_step"]
 
 EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_destroy", "cfm_model_set_option",
             "cfm_plan_masked", "cfm_plan_masked_ex", "cfm_plan_padded", "cfm_workspace_bytes_masked", "cfm_workspace_bytes_padded",
@@ -172,6 +185,7 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_fbank_create", "cfm_fbank_destroy", "cfm_fbank_num_frames", "cfm_fbank_compute",
             "cfm_rnnt_create", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
             "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error",
+            "cfm_rnnt_beam_workspace_bytes", "cfm_rnnt_beam_search", "cfm_rnnt_beam_error",
             "cfm_cls_create", "cfm_cls_destroy", "cfm_cls_pool_workspace_bytes", "cfm_cls_workspace_bytes",
             "cfm_cls_pool", "cfm_cls_classify",
             "cfm_ctc_topk_workspace_bytes", "cfm_ctc_topk_slab_rows", "cfm_ctc_topk", "cfm_ctc_topk_logp",

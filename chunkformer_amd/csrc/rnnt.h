@@ -1,0 +1,62 @@
+// The cfm_rnnt handle (csrc/rnnt.hip creates it): the predictor / joint weights on the device, shared by the greedy
+// search (rnnt.hip) and the prefix beam search (rnnt_beam.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <vector>
+
+#include "../../include/cfm.h"
+
+namespace cfm {
+
+constexpr int RNNT_MAXL = 4;   // LSTM layers
+
+struct RnntDev {
+  const float* embed;                     // [V, E]
+  const float* wg[RNNT_MAXL];             // [(in_l + H), 4H]: W_ih^T rows then W_hh^T rows
+  const float* bg[RNNT_MAXL];             // [4H] b_ih + b_hh
+  const float *wp, *bp;                   // [H, J], [J]: projection and pred_ffn composed (P = J)
+  const float *wo, *bo;                   // [J, Vp] (zero-padded columns), [Vp] (padding -inf)
+  int V, Vp, E, H, nl, P, J, blank;
+};
+
+struct RnntGrid {
+  const float4* wg[RNNT_MAXL];  // per layer, block-major [K_l][n_b] slices of gate quads (i, f, g, o of a unit)
+  const float4* bg[RNNT_MAXL];  // [H] gate-quad biases (b_ih + b_hh)
+  const float4 *wp, *wo;        // block-major slices of the composed projection + pred_ffn and ffn_out columns
+  int G;
+};
+
+}  // namespace cfm
+
+struct cfm_rnnt {
+  cfm_rnnt_config cfg;
+  int device = 0;
+  void* dev_mem = nullptr;
+  cfm::RnntDev w{};
+  const float *we = nullptr, *be = nullptr;   // enc_ffn [J, Eenc] (torch layout), [J]
+  // the grid path's block-major slices (built for grid_blocks workgroups per utterance)
+  int grid_blocks = 32;                       // 0: always one workgroup per utterance
+  int grid_lds = 1;                           // cache the grid path's weight slices in LDS when they fit
+  int grid_atomic = 1;                        // exchanged vectors by agent-scope atomics, no cache-wide fences
+  int grid_force_error = 0;                   // test hook: the grid search starts with its error word set
+  int n_cu = 0;
+  void* grid_mem = nullptr;
+  cfm::RnntGrid gw{};
+  std::vector<std::vector<float>> host_wg;    // [(in_l + H)][4H] transposed gate weights per layer
+  std::vector<std::vector<float>> host_bg;    // [4H]
+  std::vector<float> host_wp, host_wo;   // [H][J] (projection + pred_ffn composed), [J][Vp]
+  // the beam search's GEMM operands in nn.Linear layout [N][K] (rnnt_beam.hip builds them on its first call, under
+  // beam_mu, from the host copies above): per layer [4H][in_l + H], composed projection [J][H], ffn_out [V][J]
+  std::mutex beam_mu;
+  void* beam_mem = nullptr;
+  const float* bw_g[cfm::RNNT_MAXL] = {};
+  const float *bw_p = nullptr, *bw_o = nullptr;
+  ~cfm_rnnt() {
+    (void)hipSetDevice(device);
+    if (dev_mem) (void)hipFree(dev_mem);
+    if (grid_mem) (void)hipFree(grid_mem);
+    if (beam_mem) (void)hipFree(beam_mem);
+  }
+};

@@ -32,23 +32,13 @@
 #include "../../include/cfm.h"
 #include "cfm_common.h"
 #include "cfm_kernels.h"
+#include "rnnt.h"
 #include "status.h"
 
 namespace cfm {
 
 constexpr int RNNT_NT = 512;   // threads per workgroup (8 waves)
 constexpr int RNNT_RF = 8;     // frames per joint block
-constexpr int RNNT_MAXL = 4;   // LSTM layers
-
-struct RnntDev {
-  const float* embed;                     // [V, E]
-  const float* wg[RNNT_MAXL];             // [(in_l + H), 4H]: W_ih^T rows then W_hh^T rows
-  const float* bg[RNNT_MAXL];             // [4H] b_ih + b_hh
-  const float *wp, *bp;                   // [H, J], [J]: projection and pred_ffn composed (P = J)
-  const float *wo, *bo;                   // [J, Vp] (zero-padded columns), [Vp] (padding -inf)
-  int V, Vp, E, H, nl, P, J, blank;
-};
-
 // y[0:M) = WT^T x + bias (WT [K][M] row-major, M % 4 == 0); x, y, red in LDS.  Outputs are split
 // into float4 groups; when there are fewer groups than threads the K range is split too and the
 // partial sums reduced through `red` ([ks][M] floats).
@@ -250,13 +240,6 @@ __global__ __launch_bounds__(RNNT_NT) void rnnt_greedy_kernel(RnntDev w, const f
 constexpr int RG_NT = 256;     // threads per workgroup (4 waves)
 constexpr int RG_MAXB = 32;    // utterances on the grid path (B * G <= CUs)
 constexpr int RG_MAXG = 256;   // workgroups per utterance
-
-struct RnntGrid {
-  const float4* wg[RNNT_MAXL];  // per layer, block-major [K_l][n_b] slices of gate quads (i, f, g, o of a unit)
-  const float4* bg[RNNT_MAXL];  // [H] gate-quad biases (b_ih + b_hh)
-  const float4 *wp, *wo;        // block-major slices of the composed projection + pred_ffn and ffn_out columns
-  int G;
-};
 
 // the contiguous range of M4 output groups owned by part p of G
 CFM_DEV void rg_range(int M4, int G, int p, int& g0, int& n) {
@@ -626,30 +609,6 @@ size_t rnnt_lds_bytes(const RnntDev& w) {
 }
 
 }  // namespace cfm
-
-struct cfm_rnnt {
-  cfm_rnnt_config cfg;
-  int device = 0;
-  void* dev_mem = nullptr;
-  cfm::RnntDev w{};
-  const float *we = nullptr, *be = nullptr;   // enc_ffn [J, Eenc] (torch layout), [J]
-  // the grid path's block-major slices (built for grid_blocks workgroups per utterance)
-  int grid_blocks = 32;                       // 0: always one workgroup per utterance
-  int grid_lds = 1;                           // cache the grid path's weight slices in LDS when they fit
-  int grid_atomic = 1;                        // exchanged vectors by agent-scope atomics, no cache-wide fences
-  int grid_force_error = 0;                   // test hook: the grid search starts with its error word set
-  int n_cu = 0;
-  void* grid_mem = nullptr;
-  cfm::RnntGrid gw{};
-  std::vector<std::vector<float>> host_wg;    // [(in_l + H)][4H] transposed gate weights per layer
-  std::vector<std::vector<float>> host_bg;    // [4H]
-  std::vector<float> host_wp, host_wo;   // [H][J] (projection + pred_ffn composed), [J][Vp]
-  ~cfm_rnnt() {
-    (void)hipSetDevice(device);
-    if (dev_mem) (void)hipFree(dev_mem);
-    if (grid_mem) (void)hipFree(grid_mem);
-  }
-};
 
 using namespace cfm;
 

@@ -25,6 +25,9 @@ rescored by the attention decoder on the device (rescore.py, cfm_aed_score).
 search on the device (transducer.py, cfm_rnnt_greedy) exactly where the reference calls
 optimized_search / batch_greedy_search (chunkformer_model.py:439-448, 533-543); their per-frame
 decisions [T, n_steps] go through get_output_with_timestamps' transducer branch (no collapse).
+With `decoding_method="rnnt_beam_search"` they run the reference's transducer prefix beam search instead
+(transducer_beam.py, cfm_rnnt_beam_search): frame-synchronous, shallow-fused with the CTC head's posterior
+(`ctc_weight` 0.3, `transducer_weight` 0.7), with n-best and token frames.
 `model: classification` checkpoints (config.yaml `model_conf.tasks`, init_model.py:106-116, with an
 optional label_mapping.json) run the reference's classification path on the device (classifier.py,
 cfm_cls_classify): masked mean pool of the encoder output over time + one linear head per task,
@@ -233,6 +236,7 @@ class ChunkFormerModel:
         if aed_config is not None and model_type == "asr_model":
             self.rescorer = AttentionRescorer(aed_config, state_dict, self.device, dtype)
         self._attention_decoder = None   # decoding_method "attention": built on first use over the rescorer's handle
+        self._rnnt_beam = None           # decoding_method "rnnt_beam_search": built on first use over self.rnnt's handle
         self.label_mapping = label_mapping
         self.char_dict = char_dict
         self.fbank_conf = dict(fbank_conf or {})
@@ -378,6 +382,27 @@ class ChunkFormerModel:
             self._attention_decoder = AttentionDecoder(self.rescorer)
         return self._attention_decoder
 
+    def _rnnt_beam_search(self):
+        """The RNNTBeamSearch of decoding_method "rnnt_beam_search" (transducer_beam.py), over the greedy search's
+        handle.  ValueError for a model that is not a transducer."""
+        if self.model_type != "transducer" or getattr(self, "rnnt", None) is None:
+            raise ValueError(f"This model is a {self.model_type} model: rnnt_beam_search needs a transducer checkpoint "
+                             "(model: transducer).")
+        if getattr(self, "_rnnt_beam", None) is None:
+            from .transducer_beam import RNNTBeamSearch
+            self._rnnt_beam = RNNTBeamSearch(self.rnnt)
+        return self._rnnt_beam
+
+    def _rnnt_beam_rows(self, rows: torch.Tensor, starts, lens, beam_size: int, ctc_weight: Optional[float],
+                        transducer_weight: Optional[float]):
+        """One CTC log-softmax call (none at ctc_weight 0) and one search call over packed encoder rows."""
+        cw = 0.3 if ctc_weight is None else float(ctc_weight)
+        tw = 0.7 if transducer_weight is None else float(transducer_weight)
+        logp = None
+        if cw > 0:
+            logp, _ = self.encoder.ctc_log_softmax(rows, want_logp=True, want_ids=False)
+        return self._rnnt_beam_search().search_packed(rows, logp, starts, lens, beam_size, cw, tw)
+
     def _beam_method(self, decoding_method: str) -> bool:
         """True for "ctc_prefix_beam_search" and "attention_rescoring" (CTC checkpoints only; the latter needs the
         checkpoint's attention decoder), False for the greedy default."""
@@ -411,7 +436,8 @@ class ChunkFormerModel:
                        cuda_graph: bool = True, pipeline: Optional[bool] = None,
                        pipeline_depth: Optional[int] = None, decoding_method: str = "ctc_greedy_search",
                        beam_size: int = 10, context_graph=None, return_nbest: bool = False,
-                       ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
+                       transducer_weight: Optional[float] = None, ctc_weight: Optional[float] = None,
+                       reverse_weight: Optional[float] = None,
                        length_penalty: float = 0.0, max_len: Optional[int] = None):
         """chunkformer_model.py:321-459.  Segments of `total_batch_duration` seconds (halved,
         like the reference) go through forward_parallel_chunk with the attention/conv caches
@@ -436,11 +462,18 @@ class ChunkFormerModel:
         decoding_method "attention": the attention decoder's own beam search (attention_decode.py; `beam_size`,
         `length_penalty`, `max_len`) over the concatenated rows as one utterance; more than 5,000 rows need
         `max_len`.  The hypothesis carries no frame times: the text comes back as one string (the DecodeResult
-        without a char_dict; `return_nbest`: the N final hypotheses in final-score order)."""
+        without a char_dict; `return_nbest`: the N final hypotheses in final-score order).
+        decoding_method "rnnt_beam_search" (transducer checkpoints): the transducer prefix beam search
+        (transducer_beam.py; `beam_size` 1 .. 16, `ctc_weight` default 0.3, `transducer_weight` default 0.7) over the
+        concatenated rows as one utterance; the sentence split places the best hypothesis' tokens at the frames
+        that appended them, `return_nbest` gives the final beam."""
         self._require_asr("endless_decode")
         attention = decoding_method == "attention"
         searcher = self._attention_search() if attention else None
-        beam = False if attention else self._beam_method(decoding_method)
+        rnnt_beam = decoding_method == "rnnt_beam_search"
+        if rnnt_beam:
+            self._rnnt_beam_search()
+        beam = False if attention or rnnt_beam else self._beam_method(decoding_method)
         rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
@@ -499,6 +532,23 @@ class ChunkFormerModel:
             # decisions [1, T, n_steps], text by get_output_with_timestamps' transducer branch
             enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
             T = enc_all.shape[0]
+            if rnnt_beam:
+                best = self._rnnt_beam_rows(enc_all, [0], [T], beam_size, ctc_weight, transducer_weight)[0]
+                if self.char_dict is None:
+                    res = best
+                elif return_nbest:
+                    res = [class2str(h, self.char_dict).strip() for h in best.nbest]
+                else:
+                    # the greedy path's sentence split over a dense [T, 1] array: at most one token per frame
+                    dense = np.zeros((T, 1), dtype=np.int64)
+                    dense[np.asarray(best.times, dtype=np.int64), 0] = np.asarray(best.tokens, dtype=np.int64)
+                    res = format_segments(transducer_segments(dense, max_silence_frames(max_silence_duration)),
+                                          self.char_dict)
+                    if not return_timestamps:
+                        res = " ".join(item["decode"] for item in res).strip()
+                if return_encoder_out:
+                    return res, enc_all.unsqueeze(0)
+                return res
             dense = self.rnnt.greedy_packed(enc_all, [0], [T])
             tokens = dense.long().reshape(1, T, -1)
             if self.char_dict is not None:
@@ -565,7 +615,8 @@ class ChunkFormerModel:
                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
                      total_batch_duration: int = 1800, decoding_method: str = "ctc_greedy_search",
                      beam_size: int = 10, context_graph=None, return_nbest: bool = False,
-                     ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
+                     transducer_weight: Optional[float] = None, ctc_weight: Optional[float] = None,
+                     reverse_weight: Optional[float] = None,
                      length_penalty: float = 0.0, max_len: Optional[int] = None):
         """chunkformer_model.py:462-552 (asr_model branch): budget grouping, one masked-batch
         encoder call per group, CTC argmax, per-utterance split to its subsampled length.
@@ -578,11 +629,17 @@ class ChunkFormerModel:
         model_conf; with `return_nbest` the n-best comes back re-ranked by the rescored totals.
         decoding_method "attention" (asr_model.py's `attention` mode): the attention decoder's own beam search
         (attention_decode.py), one device search per masked batch over the same packed rows, every utterance
-        stopping at its own row count (or `max_len`); `beam_size` (1 .. 16), `length_penalty`."""
+        stopping at its own row count (or `max_len`); `beam_size` (1 .. 16), `length_penalty`.
+        decoding_method "rnnt_beam_search" (transducer checkpoints): per masked batch one CTC log-softmax call
+        (none at `ctc_weight` 0) and one transducer prefix beam search over the packed rows (transducer_beam.py;
+        `ctc_weight` default 0.3, `transducer_weight` default 0.7, `return_nbest` as for the CTC beam search)."""
         self._require_asr("batch_decode")
         attention = decoding_method == "attention"
         searcher = self._attention_search() if attention else None
-        beam = False if attention else self._beam_method(decoding_method)
+        rnnt_beam = decoding_method == "rnnt_beam_search"
+        if rnnt_beam:
+            self._rnnt_beam_search()
+        beam = False if attention or rnnt_beam else self._beam_method(decoding_method)
         rescoring = decoding_method == "attention_rescoring"
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
@@ -603,6 +660,17 @@ class ChunkFormerModel:
                 # batch_greedy_search over each utterance's rows (chunkformer_model.py:533-543): the
                 # packed rows go straight in (no pad_sequence), one workgroup per utterance
                 starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+                if rnnt_beam:
+                    results = self._rnnt_beam_rows(eo.reshape(-1, eo.shape[-1]), starts, el_rnnt, beam_size, ctc_weight,
+                                                   transducer_weight)
+                    for r in results:
+                        if self.char_dict is None:
+                            decodes.append(r)
+                        elif return_nbest:
+                            decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
+                        else:
+                            decodes.append(class2str(r.tokens, self.char_dict).strip())
+                    continue
                 dense = self.rnnt.greedy_packed(eo.reshape(-1, eo.shape[-1]), starts, el_rnnt).cpu()
                 hyps = [dense[s0: s0 + n].reshape(-1) for s0, n in zip(starts, el_rnnt)]
                 hyps = [h[h != self.rnnt.cfg.blank].tolist() for h in hyps]

@@ -384,6 +384,34 @@ int32_t cfm_rnnt_grid_blocks(const cfm_rnnt* h, int32_t B);
  * stopped early and its output is incomplete); -1 if the word could not be read.  Synchronous. */
 int32_t cfm_rnnt_error(const cfm_rnnt* h, const void* workspace, int32_t rows);
 
+/* ---- Transducer prefix beam search (the reference's mode rnnt_beam_search: transducer/search/
+ * prefix_beam_search.py:41-146) over the same handle, every utterance of the packed batch at once (csrc/rnnt_beam.hip).
+ * Frame-synchronous, one predictor + joint step per hypothesis and frame, shallow-fused with the frame's CTC posterior:
+ * logp = log(transducer_weight * p_rnnt + ctc_weight * p_ctc) in f32; candidate scores f32(score) + logp in f32,
+ * prefix fusion (log_add) and ranking in f64, ties by creation order; top-k by (value descending, index ascending).
+ *   enc_dev [rows, enc_dim] f32; ctc_logp_dev [rows, vocab] f32 (what cfm_ctc_logprobs writes) or null with
+ *   ctc_weight == 0; utterance b = rows [row_start[b], + row_len[b]) (device int32 [B]); max_len >= every row_len
+ *   (the host's frame count); beam 1 .. 16 and <= vocab; weights >= 0, not both 0.  embed_size, hidden_size and
+ *   join_dim must be multiples of 32 (CFM_ERR_ASSERT otherwise).
+ * Outputs, for up to `beam` hypotheses per utterance in final (score-descending) order:
+ *   out_tokens / out_times [beam, rows] int32: hypothesis k of utterance b at [k * rows + row_start[b] ..), the frame
+ *   at which each token was appended beside it; out_len [B, beam]; out_score [B, beam] f64; n_hyps [B].
+ * Trace (all five arrays or none; row = row_start[b] + t): trace_parent / trace_token / trace_score [rows, beam]: the
+ *   beam after frame t (parent slot, appended token or blank for an unchanged hypothesis, score; -1 parents past the
+ *   count); trace_topv / trace_topi [rows, beam, beam]: the fused top-k of each hypothesis entering frame t.
+ * Stream-ordered, no allocation after the handle's first search, no host synchronisation.  The first int32 of the
+ * workspace is an error word: 0, or 1 = a row range outside the rows or longer than max_len (searched as empty),
+ * 2 = trie map full, 3 = empty beam, 4 = NaN score (ranked as -inf); the error accessor below reads it
+ * (synchronous). */
+size_t cfm_rnnt_beam_workspace_bytes(const cfm_rnnt* h, int32_t rows, int32_t B, int32_t beam);
+cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc_dev, int32_t rows, const float* ctc_logp_dev,
+                                const int32_t* row_start_dev, const int32_t* row_len_dev, int32_t B, int32_t max_len,
+                                int32_t beam, float ctc_weight, float transducer_weight, int32_t* out_tokens,
+                                int32_t* out_times, int32_t* out_len, double* out_score, int32_t* n_hyps,
+                                int32_t* trace_parent, int32_t* trace_token, double* trace_score, float* trace_topv,
+                                int32_t* trace_topi, void* workspace, size_t workspace_bytes, cfm_stream stream);
+int32_t cfm_rnnt_beam_error(const void* workspace);
+
 /* ---- classification consumer (model: classification checkpoints): masked mean pool over time of the
  * encoder output and the per-task linear heads, the reference's SpeechClassificationModel
  * _average_pooling + classify (modules/classification_model.py:174-200, 232-281), on packed rows:

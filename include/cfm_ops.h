@@ -90,6 +90,28 @@ cfm_status cfm_op_decode_attention(int32_t dtype, int32_t kernel, const void* q,
                                    int32_t ancestry_ld, int32_t n_keys, const int32_t* utt_start, const int32_t* utt_len,
                                    int32_t n_split, float* scratch, cfm_stream stream);
 
+/* The kernels of the transducer prefix beam search (csrc/rnnt_beam.hip), one at a time.
+ * fused_topk: per row of logits [R, V] f32: lp = log_softmax(row), f = log(transducer_weight * exp(lp) + ctc_weight *
+ *   exp(ctc_logp row)) (ctc_logp [R, V] or null: the second term is 0), the K <= 16 largest f by (value descending,
+ *   index ascending) into vals / ids [R, K].
+ * beam_prune: T frames of the expand / fuse / prune step for one utterance, from the start state ([blank], score 0):
+ *   topk_vals / topk_ids [T, K, K] are the fused top-k of the hypothesis in slot h at frame t (slots past the beam's
+ *   count are not read); trace_parent / trace_token / trace_score [T, K] receive each frame's new beam (-1 parents past
+ *   the count), n_hyps [T] its count.
+ * lstm_step: embedding, LSTM layers and the composed projection + pred_ffn for R rows: tokens [R], h_in / c_in
+ *   [num_layers, R, hidden] -> h_out / c_out, pred_out [R, join_dim]. */
+cfm_status cfm_op_rnnt_fused_topk(const float* logits, const float* ctc_logp, int32_t R, int32_t V, int32_t K,
+                                  float ctc_weight, float transducer_weight, float* vals, int32_t* ids,
+                                  cfm_stream stream);
+size_t cfm_op_rnnt_beam_prune_workspace_bytes(int32_t T, int32_t K);
+cfm_status cfm_op_rnnt_beam_prune(const float* topk_vals, const int32_t* topk_ids, int32_t T, int32_t K, int32_t blank,
+                                  int32_t* trace_parent, int32_t* trace_token, double* trace_score, int32_t* n_hyps,
+                                  void* workspace, size_t workspace_bytes, cfm_stream stream);
+size_t cfm_op_rnnt_lstm_step_workspace_bytes(const cfm_rnnt* h, int32_t R);
+cfm_status cfm_op_rnnt_lstm_step(cfm_rnnt* h, const int32_t* tokens, const float* h_in, const float* c_in, int32_t R,
+                                 float* h_out, float* c_out, float* pred_out, void* workspace, size_t workspace_bytes,
+                                 cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
