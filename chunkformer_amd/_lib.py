@@ -231,6 +231,16 @@ def i32_host(values) -> torch.Tensor:
     return torch.tensor([int(v) for v in values], dtype=torch.int32)
 
 
+def packed_ranges(row_start, row_len, rows: int, what: str):
+    """The utterances of a packed batch, utterance b = rows [row_start[b], row_start[b] + row_len[b]) of `rows` rows,
+    as two int32 CPU tensors; ValueError when the two differ in length or a range is negative or runs past `rows`
+    (`what` names the packed tensor in the message)."""
+    rs, rl = [int(v) for v in row_start], [int(v) for v in row_len]
+    if len(rs) != len(rl) or any(s < 0 or n < 0 or s + n > rows for s, n in zip(rs, rl)):
+        raise ValueError(f"utterance row ranges exceed the {what}")
+    return torch.tensor(rs, dtype=torch.int32), torch.tensor(rl, dtype=torch.int32)
+
+
 def plan_masked(lens, offsets, C: int, L: int, R: int, mask_lens=None):
     """Host planner (no GPU): returns (plan int32 CPU tensor, n_chunks list, out_lens list).
     lens: feature rows per utterance; mask_lens: xs_origin_lens when it differs (None = lens)."""

@@ -277,11 +277,10 @@ def align_packed(logp: torch.Tensor, row_start, row_len, targets: Sequence[Seque
     naming the utterance indices, when a target holds the blank or an id outside the vocabulary, when
     an utterance has no alignment or no finite path -- raised after the others have been computed.
     `return_status`: no exception for those; returns (results with None for them, status per utterance)."""
+    from . import _lib
     B = len(row_start)
     rows = logp.shape[0]
-    rs, rl = [int(v) for v in row_start], [int(v) for v in row_len]
-    if any(s < 0 or n < 0 or s + n > rows for s, n in zip(rs, rl)):
-        raise ValueError("utterance row ranges exceed the log-prob tensor")
+    rs, rl = (t.tolist() for t in _lib.packed_ranges(row_start, row_len, rows, "log-prob tensor"))
     if B == 0:
         return ([], []) if return_status else []
     if logp.is_cuda:

@@ -203,16 +203,15 @@ def attention_beam_search_host(cfg: R.AEDConfig, sd: Dict[str, torch.Tensor], en
     the gap between the N-th and the (N+1)-th finite candidate -- the candidates being every row's top N + 1, so
     that beam 1 has a margin too -- and at the end the gap between the best and the
     second-best final score), `steps`, `beam_scores` / `beam_rows` (beam order, eos included)."""
+    from . import _lib
     n = _check_beam(cfg, beam_size)
     limits = step_limits(row_len, max_len)
     W = {k: v.detach().to("cpu", dtype) for k, v in R.native_names(cfg, sd).items()}
     pe = R.positional_table(cfg.d_model, R.MAX_POSITIONS, dtype)
     enc = enc_rows.detach().reshape(-1, cfg.d_model).to("cpu", dtype)
+    rs, rl = (t.tolist() for t in _lib.packed_ranges(row_start, row_len, enc.shape[0], "encoder rows"))
     out = []
-    for b, lim in enumerate(limits):
-        s, m = int(row_start[b]), int(row_len[b])
-        if s < 0 or m < 0 or s + m > enc.shape[0]:
-            raise ValueError("utterance row ranges exceed the encoder rows")
+    for s, m, lim in zip(rs, rl, limits):
         hs = HostSearch(cfg, W, pe, enc[s: s + m], n, dtype)
         hs.run(lim)
         out.append(hs.result(float(length_penalty)))
@@ -245,9 +244,10 @@ class AttentionDecoder:
             return []
         enc = enc_rows.reshape(-1, c.d_model).to(dev, torch.float32).contiguous()
         rows = enc.shape[0]
-        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
-        if check_host and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-            raise ValueError("utterance row ranges exceed the encoder rows")
+        if check_host:
+            rs, rl = _lib.packed_ranges(row_start, row_len, rows, "encoder rows")
+        else:
+            rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
         S = max(limits)
         Rn = B * n
         rs_d, rl_d, lim_d = rs.to(dev), rl.to(dev), torch.tensor(limits, dtype=torch.int32).to(dev)

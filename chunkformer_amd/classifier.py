@@ -61,11 +61,7 @@ def schema(c: ClassifierConfig) -> List[Tuple[str, Tuple[int, ...]]]:
 
 
 def _row_arrays(row_start, row_len, rows: int, device):
-    rs, rl = _lib.i32_host(row_start).reshape(-1), _lib.i32_host(row_len).reshape(-1)
-    if rs.numel() != rl.numel():
-        raise ValueError("row_start and row_len differ in length")
-    if rs.numel() and (int((rs.long() + rl.long()).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-        raise ValueError("utterance row ranges exceed the encoder rows")
+    rs, rl = _lib.packed_ranges(row_start, row_len, rows, "encoder rows")
     return rs.to(device), rl.to(device)
 
 

@@ -36,10 +36,10 @@
 #include "../../include/cfm_ops.h"
 #include "aed.h"
 #include "attn_core.h"
+#include "beam.h"
 
 namespace cfm {
 
-constexpr int ATTDEC_MAX_BEAM = 16;
 constexpr int ATTDEC_MAX_SPLIT = 16;
 enum { ADW_STATUS = 0, ADW_RUNNING = 1, ADW_INTS = 64 };
 enum { ATTDEC_ST_UTT = 2, ATTDEC_ST_LIMIT = 5 };
@@ -390,8 +390,8 @@ __global__ __launch_bounds__(256) void attdec_prune_kernel(int i, int N, int R, 
                                                            int32_t* __restrict__ tr_token, float* __restrict__ tr_score,
                                                            const int32_t* __restrict__ limit, int32_t* __restrict__ done,
                                                            int32_t* __restrict__ steps, int32_t* __restrict__ words) {
-  __shared__ int s_par[ATTDEC_MAX_BEAM], s_tok[ATTDEC_MAX_BEAM];
-  __shared__ float s_val[ATTDEC_MAX_BEAM];
+  __shared__ int s_par[BEAM_KMAX], s_tok[BEAM_KMAX];
+  __shared__ float s_val[BEAM_KMAX];
   const int u = blockIdx.x, tid = threadIdx.x;
   if (done[u]) return;
   if (tid < 64) {
@@ -412,37 +412,22 @@ __global__ __launch_bounds__(256) void attdec_prune_kernel(int i, int N, int R, 
         ctok[qd] = f ? eos : ti[(size_t)row * N + k];
       }
     }
-    uint32_t pk = 0xffffffffu;
-    int pi = -1;
+    TopKRound top;
     for (int r = 0; r < N; ++r) {
-      uint32_t bk = 0u;
-      int bi = 0x7fffffff;
 #pragma unroll
-      for (int qd = 0; qd < 4; ++qd) {
-        const int c = lane + 64 * qd;
-        if (c < N2) {
-          const uint32_t kk = key[qd];
-          const bool after = kk < pk || (kk == pk && c > pi);
-          if (after && (bi == 0x7fffffff || kk > bk || (kk == bk && c < bi))) { bk = kk; bi = c; }
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t ok = __shfl_xor(bk, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
-      }
-      pk = bk;
-      pi = bi;
-      const int sel = bi == 0x7fffffff ? 0 : bi;   // (N * N >= N candidates: always found)
+      for (int qd = 0; qd < 4; ++qd)
+        if (lane + 64 * qd < N2) top.see(key[qd], lane + 64 * qd);
+      top.reduce64();
+      const int sel = top.bi == TOPK_NONE ? 0 : top.bi;   // (N * N >= N candidates: always found)
       const int qs = sel >> 6;
       const int mine = qs == 0 ? ctok[0] : qs == 1 ? ctok[1] : qs == 2 ? ctok[2] : ctok[3];
       const int tk = __shfl(mine, sel & 63, 64);
       if (lane == 0) {
         s_par[r] = sel / N;
         s_tok[r] = tk;
-        s_val[r] = key2f(bk);
+        s_val[r] = key2f(top.bk);
       }
+      top.next();
     }
   }
   __syncthreads();
@@ -483,7 +468,7 @@ __global__ __launch_bounds__(64) void attdec_finish_kernel(int N, int R, int S, 
                                                            const int32_t* __restrict__ tr_token,
                                                            int32_t* __restrict__ tokens_out, int32_t* __restrict__ len_out,
                                                            float* __restrict__ final_out, int32_t* __restrict__ best_out) {
-  __shared__ float s_f[ATTDEC_MAX_BEAM];
+  __shared__ float s_f[BEAM_KMAX];
   const int u = blockIdx.x, j = threadIdx.x;
   if (j < N) {
     const int row = u * N + j, n = min(max(steps[u], 0), S);
@@ -618,8 +603,8 @@ struct AttDec {
     w.tr_parent = c.take<int32_t>(S * R);
     w.tr_token = c.take<int32_t>(S * R);
     w.tr_score = c.take<float>(S * R);
-    w.ti = c.take<int32_t>(R * ATTDEC_MAX_BEAM);
-    w.tv = c.take<float>(R * ATTDEC_MAX_BEAM);
+    w.ti = c.take<int32_t>(R * BEAM_KMAX);
+    w.tv = c.take<float>(R * BEAM_KMAX);
     w.x = c.take<float>(R * d);
     w.h = c.take<T>(R * d);
     w.q = c.take<T>(R * d);
@@ -720,7 +705,7 @@ struct AttDec {
 };
 
 static bool ad_geom(const cfm_aed* h, int B, int beam, int mem_rows, int max_steps, AdGeom& g) {
-  if (!h || B < 1 || beam < 1 || beam > ATTDEC_MAX_BEAM || beam > h->cfg.V || mem_rows < 0 || max_steps < 0 ||
+  if (!h || B < 1 || beam < 1 || beam > BEAM_KMAX || beam > h->cfg.V || mem_rows < 0 || max_steps < 0 ||
       max_steps > AED_MAX_POS || (int64_t)B * beam > (1 << 20))
     return false;
   if (hipSetDevice(h->device) != hipSuccess) return false;
@@ -802,7 +787,7 @@ cfm_status cfm_op_decode_attention(int32_t dtype, int32_t kernel, const void* q,
   if (dtype != CFM_DTYPE_F32 && dtype != CFM_DTYPE_BF16 && dtype != CFM_DTYPE_F16)
     return set_error(CFM_ERR_VALUE, "decode attention: unknown dtype");
   if (!q || !out || !kv) return set_error(CFM_ERR_VALUE, "decode attention: null argument");
-  if (B <= 0 || beam <= 0 || beam > ATTDEC_MAX_BEAM || H <= 0 || dk <= 0 || kv_rows <= 0)
+  if (B <= 0 || beam <= 0 || beam > BEAM_KMAX || H <= 0 || dk <= 0 || kv_rows <= 0)
     return set_error(CFM_ERR_VALUE, "decode attention: bad B / beam / H / dk / kv_rows");
   const bool takes = kernel == AD_KERNEL_CROSS_MFMA ? ad_cross_mfma_takes(dtype, dk) : (dk % 16 == 0 && dk <= 128);
   if (!takes)

@@ -3,18 +3,11 @@
 //                     as order-preserving integer keys in registers (V <= 5120) or re-read;
 //   ctc_beam_kernel   the search, one workgroup per utterance, scores in f64.
 //
-// Data structures of the search (all in the workspace, one region per utterance at an offset that is a
-// multiple of row_start[b], sized from k * row_len[b]: no allocation counters, nothing shared between
-// workgroups):
-//   trie      node id 0 = the empty prefix; node 1 + t * k + r is the prefix that survivor r of frame t
-//             created: (parent node, token).
-//   map       open addressing, 2 * k * row_len slots of node ids (0 = empty), keyed by the (parent,
-//             token) of the node a slot names.  It lives for the whole utterance, so a prefix has ONE
-//             node id however often it leaves and re-enters the beam; a prefix is identified by its
-//             node id, an extension by the looked-up node or, when there is none, by its own slot
-//             (hypothesis, token) - two extensions never name the same new prefix.
-//   times     persistent lists: node 1 + t * k + r = (previous node, frame t); 0 = the empty list.  A
-//             copy shares the pointer, an append or a replace-last makes the survivor's one node.
+// Hypothesis identity and token times are the PrefixTrie of beam.h (trie, map and time lists, one region per
+// utterance in the workspace): a prefix is identified by its node id, an extension by the looked-up node
+// or, when there is none, by its own slot (hypothesis, token) - two extensions never name the same new
+// prefix.  A time list is copied by sharing its entry; an append or a replace-last makes the survivor's
+// one entry.
 //
 // A frame: (1) one thread per (hypothesis, token) extension looks the child up; an extension whose
 // child is in the beam is folded into that hypothesis' own slot, the others are candidates of their
@@ -30,6 +23,7 @@
 #include <vector>
 
 #include "../../include/cfm.h"
+#include "beam.h"
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 #include "status.h"
@@ -43,8 +37,7 @@ namespace cfm {
 // selection orders the VALUES written (logit - lse: two logits can round to one log-prob, and then the
 // lower index comes first) as order-preserving integer keys.
 //
-// Selection by rounds: round r takes the largest (key, lowest index) that comes after round r - 1's pick
-// in that order, so nothing is marked or moved.  Over the whole row that is k passes; for NPL > 4 the
+// Selection by the rounds of beam.h (TopKRound).  Over the whole row that is k passes; for NPL > 4 the
 // rounds run over a short candidate list instead: t0 = the k-th largest of the 64 per-lane maxima (at
 // least k elements are >= t0, so every element of the top-k is), found by building t0 bit by bit from
 // ballots; the elements >= t0 are appended to the wave's LDS list (their order there does not matter),
@@ -129,44 +122,31 @@ __global__ __launch_bounds__(256) void ctc_topk_kernel(const float* __restrict__
       for (int q = 0; q < TOPK_CAND / 64; ++q) {
         const int j = lane + 64 * q;
         ck[q] = j < c ? l_key[w][j] : 0u;
-        ci[q] = j < c ? l_idx[w][j] : 0x7fffffff;
+        ci[q] = j < c ? l_idx[w][j] : TOPK_NONE;
       }
     }
   }
   if (!live) return;
 
-  uint32_t pk = 0xffffffffu;
-  int pi = -1;
+  TopKRound top;
   for (int r = 0; r < k; ++r) {
-    uint32_t bk = 0u;
-    int bi = 0x7fffffff;
-    auto see = [&](uint32_t kk, int v) {
-      const bool after = kk < pk || (kk == pk && v > pi);
-      if (after && (bi == 0x7fffffff || kk > bk || (kk == bk && v < bi))) { bk = kk; bi = v; }
-    };
     if (kList && n_list >= 0) {
 #pragma unroll
       for (int q = 0; q < TOPK_CAND / 64; ++q)
-        if (lane + 64 * q < n_list) see(ck[q], ci[q]);
+        if (lane + 64 * q < n_list) top.see(ck[q], ci[q]);
     } else if constexpr (NPL > 0) {
 #pragma unroll
       for (int i = 0; i < NPL; ++i)
-        if (lane + 64 * i < V) see(key[i], lane + 64 * i);
+        if (lane + 64 * i < V) top.see(key[i], lane + 64 * i);
     } else {
-      for (int v = lane; v < V; v += 64) see(f2key(with_lse ? p[v] - lse : p[v]), v);
+      for (int v = lane; v < V; v += 64) top.see(f2key(with_lse ? p[v] - lse : p[v]), v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint32_t ok = __shfl_xor(bk, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (oi != 0x7fffffff && (bi == 0x7fffffff || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
-    }
-    pk = bk;
-    pi = bi;
+    top.reduce64();
     if (lane == 0) {
-      vals[(size_t)row * k + r] = key2f(bk);
-      ids[(size_t)row * k + r] = bi;
+      vals[(size_t)row * k + r] = key2f(top.bk);
+      ids[(size_t)row * k + r] = top.bi;
     }
+    top.next();
   }
 }
 
@@ -217,15 +197,7 @@ CFM_DEV double ctx_step(const CtxTables& c, int state, int tok, int* next) {
 }
 
 // ----------------------------------------------------------------------------- beam search
-constexpr int KMAX = 16;
-constexpr int CMAX = KMAX * (KMAX + 1);
-constexpr double NINF = -INFINITY;
-
-CFM_DEV double log_add(double a, double b) {   // common.py:201-209 on [a, b]
-  if (a == NINF && b == NINF) return NINF;
-  const double m = a > b ? a : b;
-  return m + log(0.0 + exp(a - m) + exp(b - m));
-}
+constexpr int CMAX = BEAM_KMAX * (BEAM_KMAX + 1);
 
 // The total a candidate is ranked by.  NaN (from a NaN or +inf log-prob) compares false both ways and
 // would give several candidates one rank, so it is ranked as -inf and the error word is set: the
@@ -233,14 +205,8 @@ CFM_DEV double log_add(double a, double b) {   // common.py:201-209 on [a, b]
 // is a strict total order, and the ranks of n_valid candidates are exactly 0 .. n_valid - 1 - every beam
 // slot below min(k, n_valid) is written once before it is read.
 CFM_DEV double rank_key(double total, int32_t* err) {
-  if (total != total) { err[0] = 4; return NINF; }
+  if (total != total) { err[0] = BEAM_ERR_NAN; return NINF; }
   return total;
-}
-
-CFM_DEV uint32_t edge_hash(int par, int tok) {
-  uint32_t h = (uint32_t)par * 0x9E3779B1u ^ ((uint32_t)tok + 0x7F4A7C15u) * 0x85EBCA6Bu;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
-  return h;
 }
 
 struct BeamArgs {
@@ -251,46 +217,31 @@ struct BeamArgs {
   CtxTables ctx;
   int32_t *out_tok, *out_time, *out_len, *n_hyps;
   double* out_score;
-  int32_t *err, *node_par, *node_tok, *map, *tprev, *tframe;
+  int32_t* err;
+  TrieRegions trie;
 };
 
 __global__ __launch_bounds__(256) void ctc_beam_kernel(const BeamArgs a) {
   const int b = blockIdx.x, tid = threadIdx.x, K = a.k;
   const int start = a.row_start[b], len = a.row_len[b];
   if (start < 0 || len < 0 || (long long)start + len > a.rows) {
-    if (tid == 0) a.err[0] = 1;
+    if (tid == 0) a.err[0] = BEAM_ERR_RANGE;
     return;
   }
-  int32_t* node_par = a.node_par + (size_t)K * start;   // node id n >= 1 at [n - 1]
-  int32_t* node_tok = a.node_tok + (size_t)K * start;
-  int32_t* map = a.map + (size_t)2 * K * start;
-  const int cap = 2 * K * len;
-  int32_t* tprev = a.with_times ? a.tprev + (size_t)K * start : nullptr;
-  int32_t* tframe = a.with_times ? a.tframe + (size_t)K * start : nullptr;
+  const PrefixTrie trie(a.trie, K, start, len, a.with_times);
 
   // the beam
-  __shared__ int b_node[KMAX], b_tok[KMAX], b_ts[KMAX], b_tns[KMAX], b_tim[KMAX], b_cst[KMAX];
-  __shared__ double b_s[KMAX], b_ns[KMAX], b_vs[KMAX], b_vns[KMAX], b_sc[KMAX], b_vit[KMAX], b_csc[KMAX];
+  constexpr int KM = BEAM_KMAX;
+  __shared__ int b_node[KM], b_tok[KM], b_ts[KM], b_tns[KM], b_tim[KM], b_cst[KM];
+  __shared__ double b_s[KM], b_ns[KM], b_vs[KM], b_vns[KM], b_sc[KM], b_vit[KM], b_csc[KM];
   // the frame's candidates: slot h = hypothesis h unchanged, slot n + h * K + j = h extended by token j
   __shared__ int c_valid[CMAX], c_node[CMAX], c_par[CMAX], c_tok[CMAX], c_ts[CMAX], c_tnb[CMAX], c_tnm[CMAX],
       c_cst[CMAX], c_ord[CMAX];
   __shared__ double c_s[CMAX], c_ns[CMAX], c_vs[CMAX], c_vns[CMAX], c_csc[CMAX], c_tot[CMAX];
-  __shared__ int tk_u[KMAX], merge_h[KMAX], n_valid;
-  __shared__ double tk_p[KMAX];
+  __shared__ int tk_u[KM], merge_h[KM], n_valid;
+  __shared__ double tk_p[KM];
 
-  auto map_find = [&](int par, int tok) -> int {
-    if (cap == 0) return 0;
-    int s = (int)(edge_hash(par, tok) % (uint32_t)cap);
-    for (int probe = 0; probe < cap; ++probe) {
-      const int v = map[s];
-      if (v == 0) return 0;
-      if (node_par[v - 1] == par && node_tok[v - 1] == tok) return v;
-      s = s + 1 == cap ? 0 : s + 1;
-    }
-    return 0;
-  };
-
-  for (int i = tid; i < cap; i += 256) map[i] = 0;
+  for (int i = tid; i < trie.cap; i += 256) trie.map[i] = 0;
   if (tid == 0) {
     b_node[0] = 0; b_tok[0] = -1; b_ts[0] = 0; b_tns[0] = 0; b_tim[0] = 0; b_cst[0] = 0;
     b_s[0] = 0.0; b_ns[0] = NINF; b_vs[0] = 0.0; b_vns[0] = 0.0; b_sc[0] = 0.0; b_vit[0] = 0.0; b_csc[0] = 0.0;
@@ -314,7 +265,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const BeamArgs a) {
     if (tid < n * K) {
       const int h = tid / K, j = tid - h * K, u = tk_u[j];
       if (u != a.blank) {
-        const int child = map_find(b_node[h], u);
+        const int child = trie.find(b_node[h], u);
         int target = -1;
         if (child > 0)
           for (int h2 = 0; h2 < n; ++h2)
@@ -404,21 +355,13 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const BeamArgs a) {
       int node = c_node[i];
       if (node < 0) {
         node = fresh;
-        node_par[node - 1] = c_par[i];
-        node_tok[node - 1] = c_tok[i];
-        int s = (int)(edge_hash(c_par[i], c_tok[i]) % (uint32_t)cap), probe = 0;
-        for (; probe < cap; ++probe) {
-          if (atomicCAS(&map[s], 0, node) == 0) break;
-          s = s + 1 == cap ? 0 : s + 1;
-        }
-        if (probe == cap) a.err[0] = 2;   // cannot happen: at most K * len inserts into 2 * K * len slots
+        if (!trie.insert(node, c_par[i], c_tok[i])) a.err[0] = BEAM_ERR_MAP;
       }
       int tns = 0;
       if (a.with_times && c_tnm[i] != 0) {
         const int base = c_tnb[i];
         tns = fresh;
-        tprev[tns - 1] = c_tnm[i] == 1 ? base : (base > 0 ? tprev[base - 1] : 0);
-        tframe[tns - 1] = t;
+        trie.time_append(tns, c_tnm[i] == 1 ? base : (base > 0 ? trie.tprev[base - 1] : 0), t);   // append / replace-last
       }
       const double s = c_s[i], ns = c_ns[i], vs = c_vs[i], vns = c_vns[i];
       b_node[rank] = node; b_tok[rank] = c_tok[i]; b_ts[rank] = c_ts[i]; b_tns[rank] = tns;
@@ -433,7 +376,7 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const BeamArgs a) {
     __syncthreads();
   }
   if (failed) {
-    if (tid == 0) a.err[0] = 3;
+    if (tid == 0) a.err[0] = BEAM_ERR_EMPTY;
     return;
   }
 
@@ -445,14 +388,15 @@ __global__ __launch_bounds__(256) void ctc_beam_kernel(const BeamArgs a) {
     if (tid < n) {
       const double csc = a.has_ctx ? -a.ctx.node_score[b_cst[tid]] : b_csc[tid];
       score = b_sc[tid] + csc;
-      for (int nd = b_node[tid]; nd > 0 && L < len; nd = node_par[nd - 1]) ++L;
+      // (the walks of PrefixTrie::tokens / frames, written out: calling them measured 1% slower per frame here)
+      for (int nd = b_node[tid]; nd > 0 && L < len; nd = trie.par[nd - 1]) ++L;
       int32_t* ot = a.out_tok + (size_t)tid * a.rows + start;
       int i = L;
-      for (int nd = b_node[tid]; nd > 0 && i > 0; nd = node_par[nd - 1]) ot[--i] = node_tok[nd - 1];
+      for (int nd = b_node[tid]; nd > 0 && i > 0; nd = trie.par[nd - 1]) ot[--i] = trie.tok[nd - 1];
       if (a.with_times && a.out_time) {
         int32_t* om = a.out_time + (size_t)tid * a.rows + start;
         i = L;
-        for (int tn = b_tim[tid]; tn > 0 && i > 0; tn = tprev[tn - 1]) om[--i] = tframe[tn - 1];
+        for (int tn = b_tim[tid]; tn > 0 && i > 0; tn = trie.tprev[tn - 1]) om[--i] = trie.tframe[tn - 1];
         while (i > 0) om[--i] = -1;
       }
     }
@@ -535,13 +479,20 @@ void cfm_ctx_destroy(cfm_ctx* h) {
   delete h;
 }
 
-// header (error word) | trie parent, token [k * rows] | map [2 k * rows] | times previous, frame [k * rows]
+// header (error word) | the trie's regions (beam.h) for k * rows nodes
+static size_t beam_carve(void* ws, int rows, int k, bool with_times, BeamArgs& a) {
+  Carver c(ws);
+  a.err = c.take<int32_t>(64);
+  a.trie = carve_trie(c, (size_t)k * (size_t)rows, with_times);
+  return c.off;
+}
+
 size_t cfm_ctc_beam_workspace_bytes(int32_t rows, int32_t B, int32_t k, int32_t with_times, int32_t n_context_nodes) {
   (void)B;
   (void)n_context_nodes;   // the context tables live in the cfm_ctx handle
   if (rows < 0 || k < 1) return 0;
-  const size_t u = align_up((size_t)k * (size_t)rows * 4);
-  return 256 + 2 * u + align_up((size_t)2 * k * (size_t)rows * 4) + (with_times ? 2 * u : 0);
+  BeamArgs a{};
+  return beam_carve(nullptr, rows, k, with_times != 0, a);
 }
 
 cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, int32_t rows, int32_t k,
@@ -549,7 +500,7 @@ cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, 
                                const cfm_ctx* context, int32_t* out_tokens, int32_t* out_times, int32_t* out_len,
                                double* out_score, int32_t* n_hyps, void* ws, size_t wsb, cfm_stream stream) {
   if (B < 0 || rows < 0) return set_error(CFM_ERR_VALUE, "bad rows / B");
-  if (k < 1 || k > KMAX) return set_error(CFM_ERR_VALUE, "beam size: 1 .. 16");
+  if (k < 1 || k > BEAM_KMAX) return set_error(CFM_ERR_VALUE, "beam size: 1 .. 16");
   if ((size_t)k * (size_t)rows > (size_t)0x3fffffff) return set_error(CFM_ERR_VALUE, "k * rows exceeds the node id range");
   if (B == 0) return CFM_OK;
   if ((rows > 0 && (!topk_logp || !topk_ids)) || !row_start || !row_len || !out_tokens || !out_len || !out_score ||
@@ -566,13 +517,7 @@ cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, 
   a.rows = rows; a.k = k; a.blank = blank_id; a.has_ctx = context != nullptr; a.with_times = with_times;
   if (context) a.ctx = context->t;
   a.out_tok = out_tokens; a.out_time = out_times; a.out_len = out_len; a.out_score = out_score; a.n_hyps = n_hyps;
-  const size_t u = align_up((size_t)k * (size_t)rows * 4);
-  char* p = (char*)ws;
-  a.err = (int32_t*)p; p += 256;
-  a.node_par = (int32_t*)p; p += u;
-  a.node_tok = (int32_t*)p; p += u;
-  a.map = (int32_t*)p; p += align_up((size_t)2 * k * (size_t)rows * 4);
-  if (with_times) { a.tprev = (int32_t*)p; p += u; a.tframe = (int32_t*)p; }
+  beam_carve(ws, rows, k, with_times, a);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(ws, 0, 256, st);
   if (e == hipSuccess) {
@@ -586,7 +531,7 @@ cfm_status cfm_ctc_beam_search(const float* topk_logp, const int32_t* topk_ids, 
 cfm_status cfm_ctc_topk_logp(const float* logp, int32_t rows, int32_t V, int32_t k, float* topk_logp, int32_t* topk_ids,
                              cfm_stream stream) {
   if (rows < 0 || V < 1) return set_error(CFM_ERR_VALUE, "bad rows / V");
-  if (k < 1 || k > KMAX || k > V) return set_error(CFM_ERR_VALUE, "top-k: 1 <= k <= 16 and k <= V");
+  if (k < 1 || k > BEAM_KMAX || k > V) return set_error(CFM_ERR_VALUE, "top-k: 1 <= k <= 16 and k <= V");
   if (rows == 0) return CFM_OK;
   if (!logp || !topk_logp || !topk_ids) return set_error(CFM_ERR_VALUE, "null argument");
   const int e = ctc_topk_rows(logp, rows, V, k, 0, topk_logp, topk_ids, (hipStream_t)stream);

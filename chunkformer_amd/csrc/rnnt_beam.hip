@@ -19,12 +19,10 @@
 // The predictor is evaluated for every live hypothesis at every frame, as the reference does; an unchanged
 // hypothesis keeps its old state, so its next evaluation repeats the same values.
 //
-// Hypothesis identity is the trie of ctc_beam.hip: node 0 = the empty prefix, node 1 + t * K + r = the prefix that
-// survivor r of frame t created, (parent node, token); an open-addressing map of 2 K row_len slots, keyed by the
-// (parent, token) of the node a slot names, lives for the whole utterance, so a prefix has one node id however often
-// it leaves and re-enters the beam.  Token times are persistent lists as there: entry 1 + t * K + r = (previous
-// entry, frame t).  Every loop is bounded by a launch argument or a validated length; the error word (first word of
-// the workspace) is set where the reference has no answer.
+// Hypothesis identity and token times are the PrefixTrie of beam.h: a prefix has one node id however often it leaves
+// and re-enters the beam, and an appended token makes the survivor's one time entry.  Every loop is bounded by a
+// launch argument or a validated length; the error word (first word of the workspace) is set where the reference has
+// no answer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +34,7 @@
 
 #include "../../include/cfm.h"
 #include "../../include/cfm_ops.h"
+#include "beam.h"
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 #include "rnnt.h"
@@ -44,11 +43,8 @@
 
 namespace cfm {
 
-constexpr int RB_KMAX = 16;
-constexpr int RB_CMAX = RB_KMAX * RB_KMAX;
+constexpr int RB_CMAX = BEAM_KMAX * BEAM_KMAX;
 constexpr int RB_LDS_KEYS = 8192;   // rows up to this many columns keep their fused keys in LDS
-constexpr double RB_NINF = -INFINITY;
-enum { RB_ERR_RANGE = 1, RB_ERR_MAP = 2, RB_ERR_EMPTY = 3, RB_ERR_NAN = 4 };
 
 // which rows a kernel touches: utterance b's slots k < n[b] while t < ulen[b]; all of them with ulen == null
 struct RbLive {
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(64) void rb_init_kernel(const int32_t* __restrict__
   if (b >= B) return;
   int s = row_start[b], len = row_len[b];
   if (s < 0 || len < 0 || s > rows || len > rows - s || len > max_len) {
-    err[0] = RB_ERR_RANGE;
+    err[0] = BEAM_ERR_RANGE;
     s = 0;
     len = 0;
   }
@@ -134,8 +130,10 @@ __global__ __launch_bounds__(128) void rb_joint_in_kernel(RbLive lv, const float
 // One workgroup per row.  lp = (x - max) - log(sum exp(x - max)) as torch.log_softmax forms it, then
 // f = log(tw exp(lp) + cw exp(ctc)) (no CTC row: the second term is 0), all f32.  The K largest f by (value
 // descending, index ascending) are taken in K rounds over order-preserving keys: round q takes the largest key that
-// comes after round q - 1's pick in that order, so nothing is marked or moved.  The keys are formed once into LDS
-// (V <= RB_LDS_KEYS) or formed again in every round; the fused row is never written to memory.
+// comes after round q - 1's pick in that order, so nothing is marked or moved (the rounds of beam.h's TopKRound,
+// written out here: with TopKRound this kernel measured 0.1% slower on a one-utterance search, where its latency is on
+// the critical path of every frame).  The keys are formed once into LDS (V <= RB_LDS_KEYS) or formed again in every
+// round; the fused row is never written to memory.
 __global__ __launch_bounds__(256) void rb_fuse_topk_kernel(RbLive lv, const float* __restrict__ logits,
                                                            const float* __restrict__ ctc, int V, int K, float cw,
                                                            float tw, float* __restrict__ vals, int32_t* __restrict__ ids,
@@ -176,17 +174,17 @@ __global__ __launch_bounds__(256) void rb_fuse_topk_kernel(RbLive lv, const floa
   int pi = -1;
   for (int q = 0; q < K; ++q) {
     uint32_t bk = 0u;
-    int bi = 0x7fffffff;
+    int bi = TOPK_NONE;
     for (int v = tid; v < V; v += 256) {
       const uint32_t kk = cached ? rb_keys[v] : fused(v);
       const bool after = kk < pk || (kk == pk && v > pi);
-      if (after && (bi == 0x7fffffff || kk > bk)) { bk = kk; bi = v; }   // v ascends: the first of equal keys stays
+      if (after && (bi == TOPK_NONE || kk > bk)) { bk = kk; bi = v; }   // v ascends: the first of equal keys stays
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const uint32_t ok = __shfl_xor(bk, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (oi != 0x7fffffff && (bi == 0x7fffffff || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
+      if (oi != TOPK_NONE && (bi == TOPK_NONE || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
     }
     if (lane == 0) { s_k[q & 1][wid] = bk; s_i[q & 1][wid] = bi; }
     __syncthreads();
@@ -196,13 +194,13 @@ __global__ __launch_bounds__(256) void rb_fuse_topk_kernel(RbLive lv, const floa
     for (int w = 1; w < 4; ++w) {
       const uint32_t ok = s_k[q & 1][w];
       const int oi = s_i[q & 1][w];
-      if (oi != 0x7fffffff && (bi == 0x7fffffff || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
+      if (oi != TOPK_NONE && (bi == TOPK_NONE || ok > bk || (ok == bk && oi < bi))) { bk = ok; bi = oi; }
     }
     pk = bk;
     pi = bi;
     if (tid == 0) {
-      const int id = bi == 0x7fffffff ? 0 : bi;   // (K <= V: a round always finds one)
-      const float f = bi == 0x7fffffff ? -INFINITY : key2f(bk);
+      const int id = bi == TOPK_NONE ? 0 : bi;   // (K <= V: a round always finds one)
+      const float f = bi == TOPK_NONE ? -INFINITY : key2f(bk);
       vals[(size_t)r * K + q] = f;
       ids[(size_t)r * K + q] = id;
       if (tr_v) {
@@ -215,24 +213,12 @@ __global__ __launch_bounds__(256) void rb_fuse_topk_kernel(RbLive lv, const floa
 }
 
 // ----------------------------------------------------------------------------- expansion, prefix fusion, prune
-CFM_DEV double rb_log_add(double a, double b) {   // utils/common.py log_add on [a, b]
-  if (a == RB_NINF && b == RB_NINF) return RB_NINF;
-  const double m = a > b ? a : b;
-  return m + log(0.0 + exp(a - m) + exp(b - m));
-}
-
-CFM_DEV uint32_t rb_edge_hash(int par, int tok) {
-  uint32_t h = (uint32_t)par * 0x9E3779B1u ^ ((uint32_t)tok + 0x7F4A7C15u) * 0x85EBCA6Bu;
-  h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12;
-  return h;
-}
-
 struct RbBeam {
   int K, blank;
   const int32_t *ustart, *ulen;
   int32_t *err, *n, *node, *tok, *tptr, *par, *chg;
   double* score;
-  int32_t *node_par, *node_tok, *map, *tprev, *tframe;   // per-utterance regions at K (map: 2 K) * ustart
+  TrieRegions trie;
   int32_t *tr_parent, *tr_token;                          // optional trace [rows, K]
   double* tr_score;
 };
@@ -247,32 +233,15 @@ __global__ __launch_bounds__(256) void rb_prune_kernel(const RbBeam a, int t, co
   const int b = blockIdx.x, tid = threadIdx.x, K = a.K;
   const int len = a.ulen[b], start = a.ustart[b];
   if (t >= len) return;
-  int32_t* node_par = a.node_par + (size_t)K * start;   // node id v >= 1 at [v - 1]
-  int32_t* node_tok = a.node_tok + (size_t)K * start;
-  int32_t* map = a.map + (size_t)2 * K * start;
-  int32_t* tprev = a.tprev + (size_t)K * start;
-  int32_t* tframe = a.tframe + (size_t)K * start;
-  const int cap = 2 * K * len;
+  const PrefixTrie trie(a.trie, K, start, len, true);
   const int n = min(max(a.n[b], 1), K);
   const int ncand = n * K;
 
-  __shared__ int b_node[RB_KMAX], b_tok[RB_KMAX], b_tptr[RB_KMAX];
-  __shared__ double b_sc[RB_KMAX];
+  __shared__ int b_node[BEAM_KMAX], b_tok[BEAM_KMAX], b_tptr[BEAM_KMAX];
+  __shared__ double b_sc[BEAM_KMAX];
   __shared__ int c_valid[RB_CMAX], c_node[RB_CMAX], c_tok[RB_CMAX];
   __shared__ double c_raw[RB_CMAX], c_tot[RB_CMAX];
   __shared__ int n_valid;
-
-  auto map_find = [&](int par, int tok) -> int {
-    if (cap == 0) return 0;
-    int s = (int)(rb_edge_hash(par, tok) % (uint32_t)cap);
-    for (int probe = 0; probe < cap; ++probe) {
-      const int v = map[s];
-      if (v == 0) return 0;
-      if (node_par[v - 1] == par && node_tok[v - 1] == tok) return v;
-      s = s + 1 == cap ? 0 : s + 1;
-    }
-    return 0;
-  };
 
   if (tid < n) {
     const int r = b * K + tid;
@@ -287,11 +256,11 @@ __global__ __launch_bounds__(256) void rb_prune_kernel(const RbBeam a, int t, co
     const int u = ti[(size_t)b * K * K + tid];
     const float sc = (float)b_sc[h] + tv[(size_t)b * K * K + tid];
     double tot = (double)sc;
-    if (tot != tot) { a.err[0] = RB_ERR_NAN; tot = RB_NINF; }   // NaN is ranked as -inf
+    if (tot != tot) { a.err[0] = BEAM_ERR_NAN; tot = NINF; }   // NaN is ranked as -inf
     c_raw[tid] = tot;
     c_tot[tid] = tot;
     c_tok[tid] = u;
-    c_node[tid] = u == a.blank ? b_node[h] : map_find(b_node[h], u);   // an extension: its node if it has one, else 0
+    c_node[tid] = u == a.blank ? b_node[h] : trie.find(b_node[h], u);   // an extension: its node if it has one, else 0
     c_valid[tid] = 1;
   }
   __syncthreads();
@@ -308,7 +277,7 @@ __global__ __launch_bounds__(256) void rb_prune_kernel(const RbBeam a, int t, co
       if (p >= 0) {
         const int first = min(tid, p), second = max(tid, p);
         c_valid[second] = 0;
-        c_tot[first] = rb_log_add(c_raw[first], c_raw[second]);
+        c_tot[first] = log_add(c_raw[first], c_raw[second]);
       }
     }
   }
@@ -329,18 +298,10 @@ __global__ __launch_bounds__(256) void rb_prune_kernel(const RbBeam a, int t, co
       if (ext) {
         if (node <= 0) {
           node = fresh;
-          node_par[node - 1] = b_node[h];
-          node_tok[node - 1] = u;
-          int s = (int)(rb_edge_hash(b_node[h], u) % (uint32_t)cap), probe = 0;
-          for (; probe < cap; ++probe) {
-            if (atomicCAS(&map[s], 0, node) == 0) break;
-            s = s + 1 == cap ? 0 : s + 1;
-          }
-          if (probe == cap) a.err[0] = RB_ERR_MAP;   // at most K * len inserts into 2 * K * len slots
+          if (!trie.insert(node, b_node[h], u)) a.err[0] = BEAM_ERR_MAP;
         }
         tp = fresh;
-        tprev[tp - 1] = b_tptr[h];
-        tframe[tp - 1] = t;
+        trie.time_append(tp, b_tptr[h], t);
       }
       a.node[r] = node;
       a.tok[r] = ext ? u : b_tok[h];
@@ -358,7 +319,7 @@ __global__ __launch_bounds__(256) void rb_prune_kernel(const RbBeam a, int t, co
   }
   __syncthreads();
   if (tid == 0) {
-    if (n_valid < 1) a.err[0] = RB_ERR_EMPTY;
+    if (n_valid < 1) a.err[0] = BEAM_ERR_EMPTY;
     a.n[b] = min(K, max(n_valid, 1));
   }
 }
@@ -382,8 +343,7 @@ __global__ __launch_bounds__(128) void rb_gather_kernel(RbLive lv, const int32_t
   }
 }
 
-// One thread per final slot: tokens by walking the trie, frames by walking the time list; both chains are bounded
-// by the utterance's length (one token per frame at most).
+// One thread per final slot: tokens by walking the trie, frames by walking the time list (PrefixTrie's finish walks)
 __global__ __launch_bounds__(64) void rb_finish_kernel(const RbBeam a, int rows, int32_t* __restrict__ out_tok,
                                                        int32_t* __restrict__ out_time, int32_t* __restrict__ out_len,
                                                        double* __restrict__ out_score, int32_t* __restrict__ n_hyps) {
@@ -395,20 +355,11 @@ __global__ __launch_bounds__(64) void rb_finish_kernel(const RbBeam a, int rows,
   int L = 0;
   double score = 0.0;
   if (k < n) {
-    const int32_t* node_par = a.node_par + (size_t)K * start;
-    const int32_t* node_tok = a.node_tok + (size_t)K * start;
-    const int32_t* tprev = a.tprev + (size_t)K * start;
-    const int32_t* tframe = a.tframe + (size_t)K * start;
-    const int r = b * K + k, cap = K * len;
+    const PrefixTrie trie(a.trie, K, start, len, true);
+    const int r = b * K + k;
     score = a.score[r];
-    for (int nd = a.node[r]; nd > 0 && nd <= cap && L < len; nd = node_par[nd - 1]) ++L;
-    int32_t* ot = out_tok + (size_t)k * rows + start;
-    int i = L;
-    for (int nd = a.node[r]; nd > 0 && nd <= cap && i > 0; nd = node_par[nd - 1]) ot[--i] = node_tok[nd - 1];
-    int32_t* om = out_time + (size_t)k * rows + start;
-    i = L;
-    for (int tn = a.tptr[r]; tn > 0 && tn <= cap && i > 0; tn = tprev[tn - 1]) om[--i] = tframe[tn - 1];
-    while (i > 0) om[--i] = -1;
+    L = trie.tokens(a.node[r], out_tok + (size_t)k * rows + start);
+    trie.frames(a.tptr[r], L, out_time + (size_t)k * rows + start);
   }
   out_len[(size_t)b * K + k] = L;
   out_score[(size_t)b * K + k] = score;
@@ -452,7 +403,7 @@ struct RbWS {
   int32_t *err, *ustart, *ulen, *n, *node, *tok, *tptr, *par, *chg, *ti;
   double* score;
   float* tv;
-  int32_t *node_par, *node_tok, *map, *tprev, *tframe;
+  TrieRegions trie;
   size_t zero_bytes;   // [err, enc_proj): zeroed before a search
   float* enc_proj;
   float *xh[RNNT_MAXL][2], *c[RNNT_MAXL][2], *hn[RNNT_MAXL], *cn[RNNT_MAXL];
@@ -477,11 +428,7 @@ RbWS rb_carve(const cfm_rnnt* h, void* base, int rows, int B, int K, size_t* tot
   s.score = c.take<double>(R);
   s.tv = c.take<float>(R * K);
   s.ti = c.take<int32_t>(R * K);
-  s.node_par = c.take<int32_t>(rw * K);
-  s.node_tok = c.take<int32_t>(rw * K);
-  s.map = c.take<int32_t>(2 * rw * K);
-  s.tprev = c.take<int32_t>(rw * K);
-  s.tframe = c.take<int32_t>(rw * K);
+  s.trie = carve_trie(c, rw * K, true);
   s.zero_bytes = c.off;
   s.enc_proj = c.take<float>(rw * w.J);
   s.act_off = c.off;
@@ -504,7 +451,7 @@ RbWS rb_carve(const cfm_rnnt* h, void* base, int rows, int B, int K, size_t* tot
 }
 
 bool rb_geom_ok(const cfm_rnnt* h, int rows, int B, int K) {
-  return h && rows >= 0 && B >= 0 && K >= 1 && K <= RB_KMAX && K <= h->w.V && (int64_t)B * K <= (1 << 20) &&
+  return h && rows >= 0 && B >= 0 && K >= 1 && K <= BEAM_KMAX && K <= h->w.V && (int64_t)B * K <= (1 << 20) &&
          (size_t)K * (size_t)rows <= (size_t)0x3fffffff;
 }
 
@@ -556,9 +503,7 @@ size_t rb_prune_op_carve(void* base, int T, int K, RbBeam& a, RbPruneOp& o) {
   a.node = c.take<int32_t>(K); a.tok = c.take<int32_t>(K); a.tptr = c.take<int32_t>(K);
   a.par = c.take<int32_t>(K); a.chg = c.take<int32_t>(K);
   a.score = c.take<double>(K);
-  a.node_par = c.take<int32_t>(tk); a.node_tok = c.take<int32_t>(tk);
-  a.map = c.take<int32_t>(2 * tk);
-  a.tprev = c.take<int32_t>(tk); a.tframe = c.take<int32_t>(tk);
+  a.trie = carve_trie(c, tk, true);
   return c.off;
 }
 
@@ -629,7 +574,7 @@ cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc, int32_t rows, con
   a.K = K; a.blank = w.blank; a.ustart = s.ustart; a.ulen = s.ulen;
   a.err = s.err; a.n = s.n; a.node = s.node; a.tok = s.tok; a.tptr = s.tptr; a.par = s.par; a.chg = s.chg;
   a.score = s.score;
-  a.node_par = s.node_par; a.node_tok = s.node_tok; a.map = s.map; a.tprev = s.tprev; a.tframe = s.tframe;
+  a.trie = s.trie;
   a.tr_parent = trace ? trace_parent : nullptr; a.tr_token = trace ? trace_token : nullptr;
   a.tr_score = trace ? trace_score : nullptr;
   const float* ctc = ctc_weight > 0.f ? ctc_logp : nullptr;
@@ -671,7 +616,7 @@ int32_t cfm_rnnt_beam_error(const void* ws) {
 cfm_status cfm_op_rnnt_fused_topk(const float* logits, const float* ctc_logp, int32_t R, int32_t V, int32_t K,
                                   float ctc_weight, float transducer_weight, float* vals, int32_t* ids,
                                   cfm_stream stream) {
-  if (R < 0 || V < 1 || K < 1 || K > RB_KMAX || K > V) return set_error(CFM_ERR_VALUE, "fused top-k: bad R / V / K");
+  if (R < 0 || V < 1 || K < 1 || K > BEAM_KMAX || K > V) return set_error(CFM_ERR_VALUE, "fused top-k: bad R / V / K");
   if (R == 0) return CFM_OK;
   if (!logits || !vals || !ids) return set_error(CFM_ERR_VALUE, "null argument");
   const RbLive lv{nullptr, nullptr, nullptr, K, 0};
@@ -682,7 +627,7 @@ cfm_status cfm_op_rnnt_fused_topk(const float* logits, const float* ctc_logp, in
 }
 
 size_t cfm_op_rnnt_beam_prune_workspace_bytes(int32_t T, int32_t K) {
-  if (T < 0 || K < 1 || K > RB_KMAX) return 0;
+  if (T < 0 || K < 1 || K > BEAM_KMAX) return 0;
   RbBeam a{};
   RbPruneOp o{};
   return rb_prune_op_carve(nullptr, T, K, a, o) + 256;
@@ -691,7 +636,7 @@ size_t cfm_op_rnnt_beam_prune_workspace_bytes(int32_t T, int32_t K) {
 cfm_status cfm_op_rnnt_beam_prune(const float* topk_vals, const int32_t* topk_ids, int32_t T, int32_t K, int32_t blank,
                                   int32_t* trace_parent, int32_t* trace_token, double* trace_score, int32_t* n_hyps,
                                   void* ws, size_t wsb, cfm_stream stream) {
-  if (T < 0 || K < 1 || K > RB_KMAX) return set_error(CFM_ERR_VALUE, "beam prune: bad T / K");
+  if (T < 0 || K < 1 || K > BEAM_KMAX) return set_error(CFM_ERR_VALUE, "beam prune: bad T / K");
   if (T == 0) return CFM_OK;
   if (!topk_vals || !topk_ids || !trace_parent || !trace_token || !trace_score || !n_hyps || !ws)
     return set_error(CFM_ERR_VALUE, "null argument");

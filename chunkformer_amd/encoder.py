@@ -503,9 +503,7 @@ class ChunkFormerEncoder:
         dev = self.device
         ids = ids.reshape(-1).to(dev, torch.int32).contiguous()
         rows = ids.numel()
-        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
-        if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-            raise ValueError("utterance row ranges exceed the id tensor")
+        rs, rl = _lib.packed_ranges(row_start, row_len, rows, "id tensor")
         seg_mode = max_silence is not None
         ms = int(max_silence) if seg_mode else -1
         if seg_mode and ms < 0:

@@ -200,6 +200,15 @@ def _load_features(x: Features, featurize=None) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- model
+@dataclasses.dataclass(frozen=True)
+class _Decoding:
+    """A decoding_method other than the greedy default, resolved once per call."""
+    method: str        # "ctc_prefix_beam_search", "attention_rescoring", "attention" or "rnnt_beam_search"
+    searcher: object   # the encoder (CTC prefix beam search), the AttentionDecoder or the RNNTBeamSearch
+    lens: str          # the row lengths the search runs over: "ctc" (el_ctc) or "rnnt" (el_rnnt)
+    timed: bool        # its hypotheses carry frame times (endless_decode's sentence split)
+
+
 class ChunkFormerModel:
     """encoder + CTC head, RNN-T search or classification heads; the inference API of
     chunkformer_model.py on libcfm."""
@@ -393,16 +402,6 @@ class ChunkFormerModel:
             self._rnnt_beam = RNNTBeamSearch(self.rnnt)
         return self._rnnt_beam
 
-    def _rnnt_beam_rows(self, rows: torch.Tensor, starts, lens, beam_size: int, ctc_weight: Optional[float],
-                        transducer_weight: Optional[float]):
-        """One CTC log-softmax call (none at ctc_weight 0) and one search call over packed encoder rows."""
-        cw = 0.3 if ctc_weight is None else float(ctc_weight)
-        tw = 0.7 if transducer_weight is None else float(transducer_weight)
-        logp = None
-        if cw > 0:
-            logp, _ = self.encoder.ctc_log_softmax(rows, want_logp=True, want_ids=False)
-        return self._rnnt_beam_search().search_packed(rows, logp, starts, lens, beam_size, cw, tw)
-
     def _beam_method(self, decoding_method: str) -> bool:
         """True for "ctc_prefix_beam_search" and "attention_rescoring" (CTC checkpoints only; the latter needs the
         checkpoint's attention decoder), False for the greedy default."""
@@ -419,6 +418,58 @@ class ChunkFormerModel:
                              "attention_rescoring needs a hybrid CTC / attention checkpoint. Use "
                              "ctc_prefix_beam_search or ctc_greedy_search.")
         return True
+
+    def _resolve_decoding(self, decoding_method: str) -> Optional[_Decoding]:
+        """The search of `decoding_method`, None for the greedy default; ValueError for an unknown method or one this
+        checkpoint cannot run."""
+        if decoding_method == "attention":
+            return _Decoding("attention", self._attention_search(), "ctc", timed=False)
+        if decoding_method == "rnnt_beam_search":
+            return _Decoding("rnnt_beam_search", self._rnnt_beam_search(), "rnnt", timed=True)
+        if not self._beam_method(decoding_method):
+            return None
+        return _Decoding(decoding_method, self.encoder, "ctc", timed=True)
+
+    def _search_rows(self, mode: _Decoding, rows: torch.Tensor, starts, lens, beam_size: int = 10, context_graph=None,
+                     return_nbest: bool = False, transducer_weight: Optional[float] = None,
+                     ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
+                     length_penalty: float = 0.0, max_len: Optional[int] = None):
+        """The search `mode` over packed encoder rows, utterance b = rows [starts[b], + lens[b]): one DecodeResult
+        per utterance.  The options are those of endless_decode / batch_decode."""
+        if mode.method == "attention":
+            return mode.searcher.search(rows, starts, lens, beam_size, length_penalty, max_len)
+        if mode.method == "rnnt_beam_search":
+            # one CTC log-softmax call (none at ctc_weight 0) and one search call
+            cw = 0.3 if ctc_weight is None else float(ctc_weight)
+            tw = 0.7 if transducer_weight is None else float(transducer_weight)
+            logp = None
+            if cw > 0:
+                logp, _ = self.encoder.ctc_log_softmax(rows, want_logp=True, want_ids=False)
+            return mode.searcher.search_packed(rows, logp, starts, lens, beam_size, cw, tw)
+        results = mode.searcher.ctc_prefix_beam_search(rows, starts, lens, beam_size, context_graph)
+        if mode.method == "attention_rescoring":
+            results = self.rescorer.rescore(results, rows, starts, lens, ctc_weight, reverse_weight, return_nbest)
+        return results
+
+    def _render(self, result, return_nbest: bool):
+        """What a search's DecodeResult comes back as: itself without a char_dict, the n-best texts with
+        `return_nbest`, else the text of the best hypothesis."""
+        if self.char_dict is None:
+            return result
+        if return_nbest:
+            return [class2str(h, self.char_dict).strip() for h in result.nbest]
+        return class2str(result.tokens, self.char_dict).strip()
+
+    def _render_segments(self, result, T: int, max_silence_duration: float, return_timestamps: bool):
+        """endless_decode's sentence split of a hypothesis with frame times: the reference's split over a dense
+        [T, 1] array with the tokens at their `times` frames (at most one token per frame, no duplicate removal: "a a"
+        stays two tokens); the sentences joined into one string without `return_timestamps`."""
+        dense = np.zeros((T, 1), dtype=np.int64)
+        dense[np.asarray(result.times, dtype=np.int64), 0] = np.asarray(result.tokens, dtype=np.int64)
+        res = format_segments(transducer_segments(dense, max_silence_frames(max_silence_duration)), self.char_dict)
+        if not return_timestamps:
+            res = " ".join(item["decode"] for item in res).strip()
+        return res
 
     # ---------------------------------------------------------------- API
     def encode(self, xs: torch.Tensor, xs_lens: torch.Tensor, chunk_size: Optional[int] = None,
@@ -468,13 +519,10 @@ class ChunkFormerModel:
         concatenated rows as one utterance; the sentence split places the best hypothesis' tokens at the frames
         that appended them, `return_nbest` gives the final beam."""
         self._require_asr("endless_decode")
-        attention = decoding_method == "attention"
-        searcher = self._attention_search() if attention else None
-        rnnt_beam = decoding_method == "rnnt_beam_search"
-        if rnnt_beam:
-            self._rnnt_beam_search()
-        beam = False if attention or rnnt_beam else self._beam_method(decoding_method)
-        rescoring = decoding_method == "attention_rescoring"
+        mode = self._resolve_decoding(decoding_method)
+        opts = dict(beam_size=beam_size, context_graph=context_graph, return_nbest=return_nbest,
+                    transducer_weight=transducer_weight, ctc_weight=ctc_weight, reverse_weight=reverse_weight,
+                    length_penalty=length_penalty, max_len=max_len)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -485,7 +533,7 @@ class ChunkFormerModel:
         ids, outs = [], []
         seg_len = max(stop - start for start, stop, _, _ in segs) if segs else 0
         transducer = self.model_type == "transducer"
-        want_eo = bool(return_encoder_out) or transducer or beam or attention   # the searches consume the encoder rows
+        want_eo = bool(return_encoder_out) or transducer or mode is not None   # the searches consume the encoder rows
         if pipeline is None:
             pipeline = len(segs) >= 3
         if pipeline_depth is None:
@@ -527,28 +575,23 @@ class ChunkFormerModel:
             # the caches carried out of the last segment (r_att_cache / r_cnn_cache of its
             # forward_parallel_chunk call, chunkformer_model.py:407-417)
             self.last_endless_caches = (runner.att[runner.cur], runner.cnn[runner.cur])
+        if mode is not None:
+            # the concatenated rows as one utterance
+            enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
+            T = enc_all.shape[0]
+            best = self._search_rows(mode, enc_all, [0], [T], **opts)[0]
+            if self.char_dict is None or return_nbest or not mode.timed:
+                res = self._render(best, return_nbest)
+            else:
+                res = self._render_segments(best, T, max_silence_duration, return_timestamps)
+            if return_encoder_out:
+                return res, enc_all.unsqueeze(0)
+            return res
         if transducer:
             # optimized_search over the concatenated encoder output (chunkformer_model.py:439-448):
             # decisions [1, T, n_steps], text by get_output_with_timestamps' transducer branch
             enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
             T = enc_all.shape[0]
-            if rnnt_beam:
-                best = self._rnnt_beam_rows(enc_all, [0], [T], beam_size, ctc_weight, transducer_weight)[0]
-                if self.char_dict is None:
-                    res = best
-                elif return_nbest:
-                    res = [class2str(h, self.char_dict).strip() for h in best.nbest]
-                else:
-                    # the greedy path's sentence split over a dense [T, 1] array: at most one token per frame
-                    dense = np.zeros((T, 1), dtype=np.int64)
-                    dense[np.asarray(best.times, dtype=np.int64), 0] = np.asarray(best.tokens, dtype=np.int64)
-                    res = format_segments(transducer_segments(dense, max_silence_frames(max_silence_duration)),
-                                          self.char_dict)
-                    if not return_timestamps:
-                        res = " ".join(item["decode"] for item in res).strip()
-                if return_encoder_out:
-                    return res, enc_all.unsqueeze(0)
-                return res
             dense = self.rnnt.greedy_packed(enc_all, [0], [T])
             tokens = dense.long().reshape(1, T, -1)
             if self.char_dict is not None:
@@ -558,40 +601,6 @@ class ChunkFormerModel:
                     res = " ".join(item["decode"] for item in res).strip()
             else:
                 res = tokens
-            if return_encoder_out:
-                return res, enc_all.unsqueeze(0)
-            return res
-        if attention:
-            enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
-            best = searcher.search(enc_all, [0], [enc_all.shape[0]], beam_size, length_penalty, max_len)[0]
-            if self.char_dict is None:
-                res = best
-            elif return_nbest:
-                res = [class2str(h, self.char_dict).strip() for h in best.nbest]
-            else:
-                res = class2str(best.tokens, self.char_dict).strip()
-            if return_encoder_out:
-                return res, enc_all.unsqueeze(0)
-            return res
-        if beam:
-            enc_all = torch.cat(outs) if outs else torch.zeros(0, cfg.d_model, device=dev)
-            T = enc_all.shape[0]
-            best = enc.ctc_prefix_beam_search(enc_all, [0], [T], beam_size, context_graph)[0]
-            if rescoring:
-                best = self.rescorer.rescore([best], enc_all, [0], [T], ctc_weight, reverse_weight, return_nbest)[0]
-            if self.char_dict is None:
-                res = best
-            elif return_nbest:
-                res = [class2str(h, self.char_dict).strip() for h in best.nbest]
-            else:
-                # the reference's sentence split over a dense [T, 1] array with the best hypothesis' tokens
-                # at their Viterbi frames (no duplicate removal: "a a" stays two tokens)
-                dense = np.zeros((T, 1), dtype=np.int64)
-                dense[np.asarray(best.times, dtype=np.int64), 0] = np.asarray(best.tokens, dtype=np.int64)
-                res = format_segments(transducer_segments(dense, max_silence_frames(max_silence_duration)),
-                                      self.char_dict)
-                if not return_timestamps:
-                    res = " ".join(item["decode"] for item in res).strip()
             if return_encoder_out:
                 return res, enc_all.unsqueeze(0)
             return res
@@ -634,13 +643,10 @@ class ChunkFormerModel:
         (none at `ctc_weight` 0) and one transducer prefix beam search over the packed rows (transducer_beam.py;
         `ctc_weight` default 0.3, `transducer_weight` default 0.7, `return_nbest` as for the CTC beam search)."""
         self._require_asr("batch_decode")
-        attention = decoding_method == "attention"
-        searcher = self._attention_search() if attention else None
-        rnnt_beam = decoding_method == "rnnt_beam_search"
-        if rnnt_beam:
-            self._rnnt_beam_search()
-        beam = False if attention or rnnt_beam else self._beam_method(decoding_method)
-        rescoring = decoding_method == "attention_rescoring"
+        mode = self._resolve_decoding(decoding_method)
+        opts = dict(beam_size=beam_size, context_graph=context_graph, return_nbest=return_nbest,
+                    transducer_weight=transducer_weight, ctc_weight=ctc_weight, reverse_weight=reverse_weight,
+                    length_penalty=length_penalty, max_len=max_len)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -656,21 +662,16 @@ class ChunkFormerModel:
             # chunk) and, for the transducer, frames t < encoder_out_lens (none at <= 0)
             el_ctc = [len(range(int(nc) * C)[: int(n)]) for nc, n in zip(n_chunks, el.tolist())]
             el_rnnt = [max(0, int(n)) for n in el.tolist()]
+            if mode is not None:
+                starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
+                results = self._search_rows(mode, eo.reshape(-1, eo.shape[-1]), starts,
+                                            el_rnnt if mode.lens == "rnnt" else el_ctc, **opts)
+                decodes.extend(self._render(r, return_nbest) for r in results)
+                continue
             if self.model_type == "transducer":
                 # batch_greedy_search over each utterance's rows (chunkformer_model.py:533-543): the
                 # packed rows go straight in (no pad_sequence), one workgroup per utterance
                 starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
-                if rnnt_beam:
-                    results = self._rnnt_beam_rows(eo.reshape(-1, eo.shape[-1]), starts, el_rnnt, beam_size, ctc_weight,
-                                                   transducer_weight)
-                    for r in results:
-                        if self.char_dict is None:
-                            decodes.append(r)
-                        elif return_nbest:
-                            decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
-                        else:
-                            decodes.append(class2str(r.tokens, self.char_dict).strip())
-                    continue
                 dense = self.rnnt.greedy_packed(eo.reshape(-1, eo.shape[-1]), starts, el_rnnt).cpu()
                 hyps = [dense[s0: s0 + n].reshape(-1) for s0, n in zip(starts, el_rnnt)]
                 hyps = [h[h != self.rnnt.cfg.blank].tolist() for h in hyps]
@@ -678,32 +679,6 @@ class ChunkFormerModel:
                     decodes.extend(class2str(h, self.char_dict).strip() for h in hyps)
                 else:
                     decodes.extend(hyps)
-                continue
-            if attention:
-                starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
-                results = searcher.search(eo.reshape(-1, eo.shape[-1]), starts, el_ctc, beam_size, length_penalty, max_len)
-                for r in results:
-                    if self.char_dict is None:
-                        decodes.append(r)
-                    elif return_nbest:
-                        decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
-                    else:
-                        decodes.append(class2str(r.tokens, self.char_dict).strip())
-                continue
-            if beam:
-                starts = (np.cumsum([0] + list(n_chunks[:-1])) * C).tolist()
-                rows = eo.reshape(-1, eo.shape[-1])
-                results = self.encoder.ctc_prefix_beam_search(rows, starts, el_ctc, beam_size, context_graph)
-                if rescoring:
-                    results = self.rescorer.rescore(results, rows, starts, el_ctc, ctc_weight, reverse_weight,
-                                                    return_nbest)
-                for r in results:
-                    if self.char_dict is None:
-                        decodes.append(r)
-                    elif return_nbest:
-                        decodes.append([class2str(h, self.char_dict).strip() for h in r.nbest])
-                    else:
-                        decodes.append(class2str(r.tokens, self.char_dict).strip())
                 continue
             _, hyp = self.encoder.ctc_log_softmax(eo, want_logp=False)   # fused argmax head
             if self.char_dict is not None:

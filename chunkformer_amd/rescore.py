@@ -386,9 +386,10 @@ class AttentionRescorer:
             _check_hyps(c, nbest)
         enc = enc_rows.reshape(-1, c.d_model).to(dev, torch.float32).contiguous()
         rows, B = enc.shape[0], len(nbest)
-        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
-        if check_host and B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-            raise ValueError("utterance row ranges exceed the encoder rows")
+        if check_host:
+            rs, rl = _lib.packed_ranges(row_start, row_len, rows, "encoder rows")
+        else:
+            rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
         right = bool(right) and c.has_right
         toks, hs, hl, hu = [], [], [], []
         for b, hyps in enumerate(nbest):

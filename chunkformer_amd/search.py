@@ -334,11 +334,10 @@ def beam_search_topk_host(topk_logp, topk_ids, row_start, row_len, beam_size: in
         raise ValueError("top-k arrays must be [rows, beam_size]")
     if not 1 <= k <= MAX_BEAM:
         raise ValueError(f"beam size {k}: 1 .. {MAX_BEAM}")
+    from . import _lib
+    rs, rl = _lib.packed_ranges(row_start, row_len, vals.shape[0], "top-k arrays")
     out = []
-    for s0, n in zip(row_start, row_len):
-        s0, n = int(s0), int(n)
-        if s0 < 0 or n < 0 or s0 + n > vals.shape[0]:
-            raise ValueError("utterance row ranges exceed the top-k arrays")
+    for s0, n in zip(rs.tolist(), rl.tolist()):
         nbest, scores, times = _search_one(vals[s0:s0 + n].tolist(), ids[s0:s0 + n].tolist(), k, int(blank_id),
                                            context_graph)
         out.append(DecodeResult(tokens=nbest[0], score=scores[0], times=times[0], nbest=nbest, nbest_scores=scores,
@@ -347,6 +346,22 @@ def beam_search_topk_host(topk_logp, topk_ids, row_start, row_len, beam_size: in
 
 
 # ------------------------------------------------------------------------------------ device path
+def nbest_results(tok, times, lens, scores, counts, row_start) -> List[DecodeResult]:
+    """The packed n-best of a device search as DecodeResults, from host arrays: token and time planes [K, rows]
+    (hypothesis n of utterance b at [n, row_start[b] : row_start[b] + lens[b][n]]; `times` None: no times), lengths and
+    scores [B, K], hypotheses per utterance `counts` [B].  The first hypothesis is the result."""
+    tok, lens, scores = torch.as_tensor(tok), torch.as_tensor(lens).tolist(), torch.as_tensor(scores).tolist()
+    times = None if times is None else torch.as_tensor(times)
+    out = []
+    for b, (s0, n_hyp) in enumerate(zip(torch.as_tensor(row_start).tolist(), torch.as_tensor(counts).tolist())):
+        nbest = [tok[n, s0:s0 + lens[b][n]].tolist() for n in range(n_hyp)]
+        nbest_times = None if times is None else [times[n, s0:s0 + lens[b][n]].tolist() for n in range(n_hyp)]
+        sc = scores[b][:n_hyp]
+        out.append(DecodeResult(tokens=nbest[0], score=sc[0], times=None if times is None else nbest_times[0],
+                                nbest=nbest, nbest_scores=sc, nbest_times=nbest_times))
+    return out
+
+
 class _DeviceContext:
     """cfm_ctx handle of a ContextGraph on one device (cached on the graph)."""
 
@@ -404,10 +419,9 @@ def beam_search_topk_device(topk_logp: torch.Tensor, topk_ids: torch.Tensor, row
         raise ValueError("top-k arrays must be [rows, beam_size]")
     vals = topk_logp.to(torch.float32).contiguous()
     ids = topk_ids.to(torch.int32).contiguous()
-    rows, B = vals.shape[0], len(row_start)
-    rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
-    if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-        raise ValueError("utterance row ranges exceed the top-k arrays")
+    rows = vals.shape[0]
+    rs, rl = _lib.packed_ranges(row_start, row_len, rows, "top-k arrays")
+    B = rs.numel()
     if B == 0:
         return []
     ctx = _device_context(context_graph, dev)
@@ -431,18 +445,7 @@ def beam_search_topk_device(topk_logp: torch.Tensor, topk_ids: torch.Tensor, row
         what = {1: "an utterance's row range lies outside the top-k arrays",
                 4: "a score is NaN (non-finite log-probs)"}.get(err, "internal pool overflow")
         raise RuntimeError(f"CTC beam search failed (error word {err}): {what}")
-    ln_h, sc_h, nh_h = ln.cpu().tolist(), sc.cpu().tolist(), nh.cpu().tolist()
-    tok_h = tok.cpu()
-    tim_h = tim.cpu() if with_times else None
-    out = []
-    for b in range(B):
-        s0 = int(rs[b])
-        nbest = [tok_h[n, s0:s0 + ln_h[b][n]].tolist() for n in range(nh_h[b])]
-        times = [tim_h[n, s0:s0 + ln_h[b][n]].tolist() for n in range(nh_h[b])] if with_times else None
-        scores = sc_h[b][:nh_h[b]]
-        out.append(DecodeResult(tokens=nbest[0], score=scores[0], times=times[0] if with_times else None,
-                                nbest=nbest, nbest_scores=scores, nbest_times=times))
-    return out
+    return nbest_results(tok.cpu(), tim.cpu() if with_times else None, ln.cpu(), sc.cpu(), nh.cpu(), rs)
 
 
 def ctc_prefix_beam_search(ctc_probs: torch.Tensor, ctc_lens, beam_size: int,

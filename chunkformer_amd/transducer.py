@@ -232,9 +232,7 @@ class RNNTGreedy:
         enc = enc.reshape(-1, self.cfg.enc_dim).to(self.device, torch.float32).contiguous()
         rows = enc.shape[0]
         B = len(row_start)
-        rs, rl = _lib.i32_host(row_start), _lib.i32_host(row_len)
-        if B and (int((rs + rl).max()) > rows or int(rs.min()) < 0 or int(rl.min()) < 0):
-            raise ValueError("utterance row ranges exceed the encoder rows")
+        rs, rl = _lib.packed_ranges(row_start, row_len, rows, "encoder rows")
         if n_steps < 1:
             raise ValueError("n_steps must be >= 1")
         out = torch.zeros(max(rows, 1), n_steps, dtype=torch.int32, device=self.device)

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .search import DecodeResult, log_add2
+from .search import DecodeResult, log_add2, nbest_results
 from .transducer import RNNTConfig
 
 MAX_BEAM = 16
@@ -43,13 +43,6 @@ def _check_args(beam_size: int, vocab: int, ctc_weight: float, transducer_weight
         raise ValueError("ctc_weight and transducer_weight must be >= 0 and not both 0")
     if ctc_weight > 0 and not has_ctc:
         raise ValueError("ctc_weight > 0 needs the CTC log-probs (ctc_logp)")
-
-
-def _check_ranges(row_start, row_len, rows: int) -> Tuple[List[int], List[int]]:
-    rs, rl = [int(v) for v in row_start], [int(v) for v in row_len]
-    if len(rs) != len(rl) or any(s < 0 or n < 0 or s + n > rows for s, n in zip(rs, rl)):
-        raise ValueError("utterance row ranges exceed the encoder rows")
-    return rs, rl
 
 
 # ----------------------------------------------------------------------------- the step on the host
@@ -190,7 +183,8 @@ def prefix_beam_search_host(model, enc_rows: torch.Tensor, ctc_logp: Optional[to
     _check_args(beam_size, m.cfg.vocab, ctc_weight, transducer_weight, ctc is not None)
     if ctc is not None and tuple(ctc.shape) != (enc.shape[0], m.cfg.vocab):
         raise ValueError("ctc_logp must be [rows, vocab]")
-    rs, rl = _check_ranges(row_start, row_len, enc.shape[0])
+    from . import _lib
+    rs, rl = (t.tolist() for t in _lib.packed_ranges(row_start, row_len, enc.shape[0], "encoder rows"))
     use_ctc = ctc is not None and ctc_weight > 0
     del return_trace   # the host search always records it
     return [_search_one_host(m, enc[s: s + n], ctc[s: s + n] if use_ctc else None, int(beam_size), ctc_weight,
@@ -222,8 +216,8 @@ class RNNTBeamSearch:
         _check_args(K, cfg.vocab, ctc_weight, transducer_weight, ctc_logp is not None)
         enc = enc_rows.reshape(-1, cfg.enc_dim).to(dev, torch.float32).contiguous()
         rows = enc.shape[0]
-        rs, rl = _check_ranges(row_start, row_len, rows)
-        B = len(rs)
+        rs, rl = _lib.packed_ranges(row_start, row_len, rows, "encoder rows")
+        B = rs.numel()
         ctc = None
         if ctc_logp is not None and ctc_weight > 0:
             ctc = ctc_logp.reshape(-1, ctc_logp.shape[-1]).to(dev, torch.float32).contiguous()
@@ -246,29 +240,23 @@ class RNNTBeamSearch:
         if nbytes == 0:
             raise ValueError("rnnt beam search: rows / utterances / beam outside what the workspace can hold")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rs_d, rl_d = _lib.i32_host(rs).to(dev), _lib.i32_host(rl).to(dev)
+        rs_d, rl_d = rs.to(dev), rl.to(dev)
         tp = [t.data_ptr() for t in tr] if tr else [0] * 5
         with torch.cuda.device(dev):
             _lib.check(_lib.cfm_rnnt_beam_search(
-                self.rnnt._h, enc.data_ptr(), rows, _lib.ptr(ctc), rs_d.data_ptr(), rl_d.data_ptr(), B, max(rl), K,
+                self.rnnt._h, enc.data_ptr(), rows, _lib.ptr(ctc), rs_d.data_ptr(), rl_d.data_ptr(), B, int(rl.max()), K,
                 ctc_weight, transducer_weight, out_tok.data_ptr(), out_time.data_ptr(), out_len.data_ptr(),
                 out_score.data_ptr(), n_hyps.data_ptr(), *tp, ws.data_ptr(), nbytes,
                 torch.cuda.current_stream(dev).cuda_stream))
-            tok_h, time_h = out_tok.cpu().numpy(), out_time.cpu().numpy()   # (synchronises the stream)
-            len_h, score_h, n_h = out_len.cpu().tolist(), out_score.cpu().tolist(), n_hyps.cpu().tolist()
+            host = [t.cpu() for t in (out_tok, out_time, out_len, out_score, n_hyps)]   # (synchronises the stream)
             self.last_error = int(_lib.cfm_rnnt_beam_error(ws.data_ptr()))
         if self.last_error not in (0, 4):
             raise RuntimeError(f"rnnt beam search: device error word {self.last_error}")
-        tr_h = [t.cpu().numpy() for t in tr] if tr else None
-        results = []
-        for b, (s, n) in enumerate(zip(rs, rl)):
-            nb = [tok_h[k, s: s + len_h[b][k]].tolist() for k in range(n_h[b])]
-            nt = [time_h[k, s: s + len_h[b][k]].tolist() for k in range(n_h[b])]
-            sc = score_h[b][: n_h[b]]
-            res = DecodeResult(nb[0], sc[0], times=nt[0], nbest=nb, nbest_scores=sc, nbest_times=nt)
-            if tr_h:
+        results = nbest_results(*host, rs)
+        if tr:
+            tr_h = [t.cpu().numpy() for t in tr]
+            for res, s, n in zip(results, rs.tolist(), rl.tolist()):
                 res.trace = {k: v[s: s + n] for k, v in zip(("parent", "token", "score", "topv", "topi"), tr_h)}
-            results.append(res)
         return results
 
     # ---- the single kernels (include/cfm_ops.h), for the op tests and tools

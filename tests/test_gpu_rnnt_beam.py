@@ -238,3 +238,17 @@ def test_model_batch_and_endless_decode(transducer_model):
             m.encoder.ctc_log_softmax = real
     finally:
         m.char_dict = None
+
+
+@pytest.mark.parametrize("name,expected", [("v37", [7680, 40192, 2394112]), ("v130", [11264, 88064, 5496064])])
+def test_workspace_bytes_are_pinned(name, expected):
+    """cfm_rnnt_beam_workspace_bytes at (rows, B, beam) = (0, 1, 1), (65, 2, 5), (2601, 70, 10): the totals the library
+    gave before the trie regions were carved by the searches' common function (csrc/beam.h); callers size their buffers
+    from them."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from chunkformer_amd import _lib
+    from chunkformer_amd.transducer import RNNTGreedy
+    g = RNNTGreedy(*fx.model(name, "dense"), "cuda")
+    got = [int(_lib.cfm_rnnt_beam_workspace_bytes(g._h, *a)) for a in ((0, 1, 1), (65, 2, 5), (2601, 70, 10))]
+    assert got == expected

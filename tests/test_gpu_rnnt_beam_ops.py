@@ -126,6 +126,46 @@ def test_prune_hand_made_fusion_order(tb):
         np.testing.assert_allclose(dsc, sc, rtol=1e-12, atol=0)
 
 
+def reentry_case():
+    """Five frames by hand, K = 2, ids {0 = blank, 1, 2, 3}: (topv, topi, the host's beam after every frame).  The beams
+    are [(), (1,)], [(), (1, 2)], [(1,), (1, 2)], [(1, 2), (1,)], [(1, 2), (1, 2, 3)]: the prefix (1,) leaves the beam at
+    frame 1 while its extension (1, 2) stays, is created again from () at frame 2, and at frames 3 and 4 its extension
+    by 2 meets the unchanged (1, 2) -- as the earlier candidate at frame 3, as the later one at frame 4."""
+    from chunkformer_amd.transducer_beam import beam_step_host
+    frames = [
+        ([[-0.25, -0.5], [0, 0]], [[0, 1], [0, 0]]),
+        ([[-0.25, -8.0], [-0.25, -6.0]], [[0, 3], [2, 0]]),
+        ([[-0.25, -6.0], [-0.5, -8.0]], [[1, 0], [0, 3]]),
+        ([[-0.25, -1.0], [-0.25, -8.0]], [[2, 0], [0, 3]]),
+        ([[-0.25, -0.5], [-0.25, -0.5]], [[0, 3], [2, 0]]),
+    ]
+    topv = np.array([v for v, _ in frames], np.float32)
+    topi = np.array([i for _, i in frames], np.int32)
+    hyps, scores, beams = [()], [0.0], []
+    for t in range(len(frames)):
+        kept, _ = beam_step_host(hyps, scores, topv[t, :len(hyps)], topi[t, :len(hyps)], 2, 0)
+        hyps, scores = [k[0] for k in kept], [k[1] for k in kept]
+        beams.append(list(hyps))
+    return topv, topi, beams
+
+
+def test_prune_prefix_reenters_and_fuses(tb):
+    """The map lives for the whole utterance, seen from the transducer prune kernel: a prefix that left the beam and
+    is created again gets its old node back, so its next extension still meets the longer hypothesis that survived
+    and fuses with it.  With a map that forgot the prefix, frame 3 would keep (1, 2) twice."""
+    topv, topi, beams = reentry_case()
+    gone = [t for t, b in enumerate(beams) if (1,) not in b]
+    assert (1,) in beams[0] and (1,) in beams[2] and gone == [1, 4] and (1, 2) in beams[1], "no re-entry in the case"
+    assert all(len(set(b)) == 2 for b in beams)
+    par, tok, sc, cnt, fusions, _ = _host_walk(tb, topv, topi, 2)
+    assert fusions == 2 and tok[3].tolist() == [2, 0] and tok[4].tolist() == [0, 3]
+    dpar, dtok, dsc, dcnt = tb.beam_prune_device(torch.from_numpy(topv).cuda(), torch.from_numpy(topi).cuda(), 0)
+    np.testing.assert_array_equal(dcnt, cnt)
+    np.testing.assert_array_equal(dpar, par)
+    np.testing.assert_array_equal(dtok, tok)
+    np.testing.assert_allclose(dsc, sc, rtol=1e-12, atol=0)
+
+
 @pytest.mark.parametrize("name", ["v37", "v130"])
 def test_lstm_step_vs_torch(tb, name):
     """Embedding + LSTM layers + projection + pred_ffn for 21 rows against torch.nn.LSTM in f32 (1 and 2 layers)."""
