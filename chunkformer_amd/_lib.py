@@ -126,6 +126,9 @@ cfm_rnnt_beam_workspace_bytes = _sig("cfm_rnnt_beam_workspace_bytes", SZ, P, I32
 cfm_rnnt_beam_search = _sig("cfm_rnnt_beam_search", I32, P, P, I32, P, P, P, I32, I32, I32, F32, F32, P, P, P, P, P, P, P,
                             P, P, P, P, SZ, P)
 cfm_rnnt_beam_error = _sig("cfm_rnnt_beam_error", I32, P)
+# full-sum transducer score of given hypotheses over the same handle (csrc/rnnt_lattice.hip)
+cfm_rnnt_td_workspace_bytes = _sig("cfm_rnnt_td_workspace_bytes", SZ, P, I32, I32, I32, I32, I64)
+cfm_rnnt_td_score = _sig("cfm_rnnt_td_score", I32, P, P, I32, P, P, I32, P, I32, P, P, I32, I32, I64, I32, P, P, SZ, P)
 # classification consumer (include/cfm.h)
 CLS_MAX_TASKS = 16
 
@@ -173,9 +176,13 @@ cfm_op_rnnt_beam_prune_workspace_bytes = _sig("cfm_op_rnnt_beam_prune_workspace_
 cfm_op_rnnt_beam_prune = _sig("cfm_op_rnnt_beam_prune", I32, P, P, I32, I32, I32, P, P, P, P, P, SZ, P)
 cfm_op_rnnt_lstm_step_workspace_bytes = _sig("cfm_op_rnnt_lstm_step_workspace_bytes", SZ, P, I32)
 cfm_op_rnnt_lstm_step = _sig("cfm_op_rnnt_lstm_step", I32, P, P, P, P, I32, P, P, P, P, SZ, P)
+cfm_op_rnnt_lattice = _sig("cfm_op_rnnt_lattice", I32, P, I32, P, I32, P, I32, P, P, P, I32, P, P, I32, I64, P, P, P)
+cfm_op_rnnt_alpha_workspace_bytes = _sig("cfm_op_rnnt_alpha_workspace_bytes", SZ, I32, I32)
+cfm_op_rnnt_alpha = _sig("cfm_op_rnnt_alpha", I32, P, P, P, P, P, I32, I32, I64, P, P, SZ, P)
 EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_seg_attention", "cfm_op_decode_attention",
                 "cfm_op_rnnt_fused_topk", "cfm_op_rnnt_beam_prune_workspace_bytes", "cfm_op_rnnt_beam_prune",
-                "cfm_op_rnnt_lstm_step_workspace_bytes", "cfm_op_rnnt_lstm_step"]
+                "cfm_op_rnnt_lstm_step_workspace_bytes", "cfm_op_rnnt_lstm_step",
+                "cfm_op_rnnt_lattice", "cfm_op_rnnt_alpha_workspace_bytes", "cfm_op_rnnt_alpha"]
 
 EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_destroy", "cfm_model_set_option",
             "cfm_plan_masked", "cfm_plan_masked_ex", "cfm_plan_padded", "cfm_workspace_bytes_masked", "cfm_workspace_bytes_padded",
@@ -186,6 +193,7 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_rnnt_create", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
             "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error",
             "cfm_rnnt_beam_workspace_bytes", "cfm_rnnt_beam_search", "cfm_rnnt_beam_error",
+            "cfm_rnnt_td_workspace_bytes", "cfm_rnnt_td_score",
             "cfm_cls_create", "cfm_cls_destroy", "cfm_cls_pool_workspace_bytes", "cfm_cls_workspace_bytes",
             "cfm_cls_pool", "cfm_cls_classify",
             "cfm_ctc_topk_workspace_bytes", "cfm_ctc_topk_slab_rows", "cfm_ctc_topk", "cfm_ctc_topk_logp",

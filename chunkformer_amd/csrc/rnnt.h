@@ -53,10 +53,16 @@ struct cfm_rnnt {
   void* beam_mem = nullptr;
   const float* bw_g[cfm::RNNT_MAXL] = {};
   const float *bw_p = nullptr, *bw_o = nullptr;
+  // the lattice kernel's bf16 operand (rnnt_lattice.hip builds it on its first bf16 call, under lat_mu, from host_wo):
+  // ffn_out as two bf16 images [2][V][J], hi and lo = bf16(w - hi); the f32 kernel reads bw_o
+  std::mutex lat_mu;
+  void* lat_mem = nullptr;
+  int lattice_dtype = CFM_DTYPE_F32;          // "lattice_dtype": operands of cfm_rnnt_td_score's joint (f32 or bf16)
   ~cfm_rnnt() {
     (void)hipSetDevice(device);
     if (dev_mem) (void)hipFree(dev_mem);
     if (grid_mem) (void)hipFree(grid_mem);
     if (beam_mem) (void)hipFree(beam_mem);
+    if (lat_mem) (void)hipFree(lat_mem);
   }
 };

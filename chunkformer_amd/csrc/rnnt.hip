@@ -831,6 +831,12 @@ cfm_status cfm_rnnt_set_option(cfm_rnnt* h, const char* key, int64_t value) {
     h->grid_force_error = value != 0;
     return CFM_OK;
   }
+  if (std::string(key) == "lattice_dtype") {
+    if (value != CFM_DTYPE_F32 && value != CFM_DTYPE_BF16)
+      return set_error(CFM_ERR_VALUE, "lattice_dtype: CFM_DTYPE_F32 or CFM_DTYPE_BF16");
+    h->lattice_dtype = (int)value;
+    return CFM_OK;
+  }
   return set_error(CFM_ERR_VALUE, std::string("unknown rnnt option ") + key);
 }
 

@@ -38,6 +38,7 @@
 #include "cfm_common.h"
 #include "cfm_kernels.h"
 #include "rnnt.h"
+#include "rnnt_beam.h"
 #include "status.h"
 #include "workspace.h"
 
@@ -46,11 +47,6 @@ namespace cfm {
 constexpr int RB_CMAX = BEAM_KMAX * BEAM_KMAX;
 constexpr int RB_LDS_KEYS = 8192;   // rows up to this many columns keep their fused keys in LDS
 
-// which rows a kernel touches: utterance b's slots k < n[b] while t < ulen[b]; all of them with ulen == null
-struct RbLive {
-  const int32_t *ustart, *ulen, *n;
-  int K, t;
-};
 CFM_DEV bool rb_live(const RbLive& lv, int r, int* src_row) {
   if (!lv.ulen) { *src_row = r; return true; }
   const int b = r / lv.K, k = r - b * lv.K;
@@ -366,8 +362,6 @@ __global__ __launch_bounds__(64) void rb_finish_kernel(const RbBeam a, int rows,
 }
 
 // ----------------------------------------------------------------------------- host side
-namespace {
-
 // the GEMM operands in [N][K] layout, once per handle
 int rb_weights(cfm_rnnt* h) {
   std::lock_guard<std::mutex> lock(h->beam_mu);
@@ -398,18 +392,6 @@ int rb_weights(cfm_rnnt* h) {
   h->beam_mem = mem;
   return 0;
 }
-
-struct RbWS {
-  int32_t *err, *ustart, *ulen, *n, *node, *tok, *tptr, *par, *chg, *ti;
-  double* score;
-  float* tv;
-  TrieRegions trie;
-  size_t zero_bytes;   // [err, enc_proj): zeroed before a search
-  float* enc_proj;
-  float *xh[RNNT_MAXL][2], *c[RNNT_MAXL][2], *hn[RNNT_MAXL], *cn[RNNT_MAXL];
-  float *gates, *pj, *z, *logits;
-  size_t act_off, act_bytes;   // the activations: zeroed before a search (the initial LSTM state)
-};
 
 RbWS rb_carve(const cfm_rnnt* h, void* base, int rows, int B, int K, size_t* total) {
   const RnntDev& w = h->w;
@@ -482,6 +464,15 @@ cfm_status rb_predictor(const cfm_rnnt* h, const RbWS& s, const RbLive& lv, int 
   KCHK(rb_gemm(s.hn[w.nl - 1], w.H, h->bw_p, w.bp, R, w.J, w.H, s.pj, w.J, st));
   return CFM_OK;
 }
+
+int rb_init(const int32_t* row_start, const int32_t* row_len, int B, int K, int rows, int max_len, int blank,
+            const RbWS& s, hipStream_t st) {
+  hipLaunchKernelGGL(rb_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, row_start, row_len, B, K, rows, max_len,
+                     blank, s.err, s.ustart, s.ulen, s.n, s.node, s.tok, s.tptr, s.score);
+  return (int)hipGetLastError();
+}
+
+namespace {
 
 size_t rb_topk_lds(int V) { return V <= RB_LDS_KEYS ? (size_t)V * 4 : 0; }
 

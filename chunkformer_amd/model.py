@@ -28,6 +28,9 @@ decisions [T, n_steps] go through get_output_with_timestamps' transducer branch 
 With `decoding_method="rnnt_beam_search"` they run the reference's transducer prefix beam search instead
 (transducer_beam.py, cfm_rnnt_beam_search): frame-synchronous, shallow-fused with the CTC head's posterior
 (`ctc_weight` 0.3, `transducer_weight` 0.7), with n-best and token frames.
+`decoding_method="rnnt_beam_attn_rescoring"` / `"ctc_beam_td_attn_rescoring"` re-rank the n-best of that search / of
+the CTC prefix beam search by the full-sum transducer score of every hypothesis and, when the checkpoint carries
+decoder.* tensors, the attention decoder's score (transducer_rescore.py, cfm_rnnt_td_score + cfm_aed_score).
 `model: classification` checkpoints (config.yaml `model_conf.tasks`, init_model.py:106-116, with an
 optional label_mapping.json) run the reference's classification path on the device (classifier.py,
 cfm_cls_classify): masked mean pool of the encoder output over time + one linear head per task,
@@ -203,8 +206,10 @@ def _load_features(x: Features, featurize=None) -> torch.Tensor:
 @dataclasses.dataclass(frozen=True)
 class _Decoding:
     """A decoding_method other than the greedy default, resolved once per call."""
-    method: str        # "ctc_prefix_beam_search", "attention_rescoring", "attention" or "rnnt_beam_search"
-    searcher: object   # the encoder (CTC prefix beam search), the AttentionDecoder or the RNNTBeamSearch
+    method: str        # "ctc_prefix_beam_search", "attention_rescoring", "attention", "rnnt_beam_search",
+                       # "rnnt_beam_attn_rescoring" or "ctc_beam_td_attn_rescoring"
+    searcher: object   # the encoder (CTC prefix beam search), the AttentionDecoder, the RNNTBeamSearch or the
+                       # TransducerRescorer
     lens: str          # the row lengths the search runs over: "ctc" (el_ctc) or "rnnt" (el_rnnt)
     timed: bool        # its hypotheses carry frame times (endless_decode's sentence split)
 
@@ -218,7 +223,8 @@ class ChunkFormerModel:
                  resample_conf: Optional[dict] = None, model_type: str = "asr_model",
                  rnnt_config: Optional[RNNTConfig] = None, tasks: Optional[Dict[str, int]] = None,
                  classifier_config: Optional[ClassifierConfig] = None,
-                 label_mapping: Optional[Dict[str, Dict[str, str]]] = None, aed_config: Optional[AEDConfig] = None):
+                 label_mapping: Optional[Dict[str, Dict[str, str]]] = None, aed_config: Optional[AEDConfig] = None,
+                 aed_unsupported: Optional[str] = None):
         if model_type not in ("asr_model", "transducer", "classification"):
             raise AssertionError(f"model: {model_type} is not one of asr_model / transducer / classification")
         self.is_classification = model_type == "classification"
@@ -242,8 +248,12 @@ class ChunkFormerModel:
             self.classifier = ClassifierHeads(classifier_config, state_dict, self.device)
         # the attention decoder of a hybrid CTC / attention checkpoint (decoding_method "attention_rescoring")
         self.rescorer = None
-        if aed_config is not None and model_type == "asr_model":
+        if aed_config is not None and model_type in ("asr_model", "transducer"):
             self.rescorer = AttentionRescorer(aed_config, state_dict, self.device, dtype)
+        # why a transducer checkpoint's decoder.* tensors gave no rescorer (raised when a rescoring mode asks for it)
+        self._aed_unsupported = aed_unsupported
+        self._dtype = dtype
+        self._td_rescorer = None         # the transducer rescoring modes: built on first use over self.rnnt's handle
         self._attention_decoder = None   # decoding_method "attention": built on first use over the rescorer's handle
         self._rnnt_beam = None           # decoding_method "rnnt_beam_search": built on first use over self.rnnt's handle
         self.label_mapping = label_mapping
@@ -340,6 +350,11 @@ class ChunkFormerModel:
         if (model_type == "asr_model" and any(k.startswith("decoder.") for k in sd)
                 and conf.get("decoder", "transformer") in ("transformer", "bitransformer")):
             aed_cfg = AEDConfig.from_conf(conf, vocab, cfg.d_model)
+        # init_model.py:118-135 passes the decoder into the Transducer too (its attention rescoring modes); a decoder
+        # those modes cannot run must not keep the checkpoint from loading: the reason is kept for them
+        aed_reason = None
+        if model_type == "transducer":
+            aed_cfg, aed_reason = transducer_decoder_config(conf, sd, vocab, cfg.d_model)
         label_mapping = None
         lp = os.path.join(path, "label_mapping.json")
         if os.path.exists(lp):
@@ -357,7 +372,8 @@ class ChunkFormerModel:
                     char_dict[int(arr[1])] = arr[0]
         return cls(cfg, sd, dtype=dtype, device=device, char_dict=char_dict, fbank_conf=conf.get("fbank_conf"),
                    resample_conf=conf.get("resample_conf"), model_type=model_type, rnnt_config=rnnt_cfg,
-                   classifier_config=cls_cfg, label_mapping=label_mapping, aed_config=aed_cfg)
+                   classifier_config=cls_cfg, label_mapping=label_mapping, aed_config=aed_cfg,
+                   aed_unsupported=aed_reason)
 
     def get_tasks(self) -> Optional[Dict[str, int]]:
         """chunkformer_model.py:250-254: {task: classes} of a classification model, else None."""
@@ -402,6 +418,19 @@ class ChunkFormerModel:
             self._rnnt_beam = RNNTBeamSearch(self.rnnt)
         return self._rnnt_beam
 
+    def _transducer_rescoring(self, decoding_method: str):
+        """The TransducerRescorer of the modes "rnnt_beam_attn_rescoring" / "ctc_beam_td_attn_rescoring"
+        (transducer_rescore.py), over the greedy search's handle and the attention rescorer's, if the checkpoint has
+        one.  ValueError naming the mode for a model that is not a transducer."""
+        if self.model_type != "transducer" or getattr(self, "rnnt", None) is None:
+            raise ValueError(f"This model is a {self.model_type} model: {decoding_method} needs a transducer checkpoint "
+                             "(model: transducer).")
+        if getattr(self, "_td_rescorer", None) is None:
+            from .transducer_rescore import TransducerRescorer
+            self._td_rescorer = TransducerRescorer(self.rnnt, getattr(self, "rescorer", None),
+                                                   getattr(self, "_dtype", "fp32"))
+        return self._td_rescorer
+
     def _beam_method(self, decoding_method: str) -> bool:
         """True for "ctc_prefix_beam_search" and "attention_rescoring" (CTC checkpoints only; the latter needs the
         checkpoint's attention decoder), False for the greedy default."""
@@ -426,6 +455,10 @@ class ChunkFormerModel:
             return _Decoding("attention", self._attention_search(), "ctc", timed=False)
         if decoding_method == "rnnt_beam_search":
             return _Decoding("rnnt_beam_search", self._rnnt_beam_search(), "rnnt", timed=True)
+        if decoding_method == "rnnt_beam_attn_rescoring":
+            return _Decoding(decoding_method, self._transducer_rescoring(decoding_method), "rnnt", timed=True)
+        if decoding_method == "ctc_beam_td_attn_rescoring":
+            return _Decoding(decoding_method, self._transducer_rescoring(decoding_method), "ctc", timed=True)
         if not self._beam_method(decoding_method):
             return None
         return _Decoding(decoding_method, self.encoder, "ctc", timed=True)
@@ -433,9 +466,30 @@ class ChunkFormerModel:
     def _search_rows(self, mode: _Decoding, rows: torch.Tensor, starts, lens, beam_size: int = 10, context_graph=None,
                      return_nbest: bool = False, transducer_weight: Optional[float] = None,
                      ctc_weight: Optional[float] = None, reverse_weight: Optional[float] = None,
-                     length_penalty: float = 0.0, max_len: Optional[int] = None):
+                     length_penalty: float = 0.0, max_len: Optional[int] = None, attn_weight: Optional[float] = None,
+                     search_ctc_weight: Optional[float] = None, search_transducer_weight: Optional[float] = None):
         """The search `mode` over packed encoder rows, utterance b = rows [starts[b], + lens[b]): one DecodeResult
         per utterance.  The options are those of endless_decode / batch_decode."""
+        if mode.method in ("rnnt_beam_attn_rescoring", "ctc_beam_td_attn_rescoring"):
+            rescorer = mode.searcher
+            aw = (0.5 if rescorer.rescorer is not None else 0.0) if attn_weight is None else float(attn_weight)
+            if aw > 0 and rescorer.rescorer is None:
+                why = getattr(self, "_aed_unsupported", None)
+                raise ValueError(f"{mode.method} with attn_weight > 0 needs an attention decoder: "
+                                 + (f"this checkpoint's decoder is not supported ({why})." if why else
+                                    "the checkpoint holds no decoder.* tensors.") + " Pass attn_weight=0.")
+            if mode.method == "rnnt_beam_attn_rescoring":
+                scw = 0.3 if search_ctc_weight is None else float(search_ctc_weight)
+                stw = 0.7 if search_transducer_weight is None else float(search_transducer_weight)
+                logp = None
+                if scw > 0:
+                    logp, _ = self.encoder.ctc_log_softmax(rows, want_logp=True, want_ids=False)
+                results = self._rnnt_beam_search().search_packed(rows, logp, starts, lens, beam_size, scw, stw)
+            else:
+                results = self.encoder.ctc_prefix_beam_search(rows, starts, lens, beam_size, context_graph)
+            return rescorer.rescore(results, rows, starts, lens, 0.5 if ctc_weight is None else float(ctc_weight), aw,
+                                    0.5 if transducer_weight is None else float(transducer_weight), reverse_weight,
+                                    return_nbest)
         if mode.method == "attention":
             return mode.searcher.search(rows, starts, lens, beam_size, length_penalty, max_len)
         if mode.method == "rnnt_beam_search":
@@ -487,6 +541,8 @@ class ChunkFormerModel:
                        cuda_graph: bool = True, pipeline: Optional[bool] = None,
                        pipeline_depth: Optional[int] = None, decoding_method: str = "ctc_greedy_search",
                        beam_size: int = 10, context_graph=None, return_nbest: bool = False,
+                       attn_weight: Optional[float] = None, search_ctc_weight: Optional[float] = None,
+                       search_transducer_weight: Optional[float] = None,
                        transducer_weight: Optional[float] = None, ctc_weight: Optional[float] = None,
                        reverse_weight: Optional[float] = None,
                        length_penalty: float = 0.0, max_len: Optional[int] = None):
@@ -517,12 +573,16 @@ class ChunkFormerModel:
         decoding_method "rnnt_beam_search" (transducer checkpoints): the transducer prefix beam search
         (transducer_beam.py; `beam_size` 1 .. 16, `ctc_weight` default 0.3, `transducer_weight` default 0.7) over the
         concatenated rows as one utterance; the sentence split places the best hypothesis' tokens at the frames
-        that appended them, `return_nbest` gives the final beam."""
+        that appended them, `return_nbest` gives the final beam.
+        decoding_method "rnnt_beam_attn_rescoring" / "ctc_beam_td_attn_rescoring": as in batch_decode, over the
+        concatenated rows as one utterance; `attn_weight`, `search_ctc_weight` and `search_transducer_weight` must be
+        passed by keyword (see batch_decode)."""
         self._require_asr("endless_decode")
         mode = self._resolve_decoding(decoding_method)
         opts = dict(beam_size=beam_size, context_graph=context_graph, return_nbest=return_nbest,
                     transducer_weight=transducer_weight, ctc_weight=ctc_weight, reverse_weight=reverse_weight,
-                    length_penalty=length_penalty, max_len=max_len)
+                    length_penalty=length_penalty, max_len=max_len, attn_weight=attn_weight,
+                    search_ctc_weight=search_ctc_weight, search_transducer_weight=search_transducer_weight)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -624,6 +684,8 @@ class ChunkFormerModel:
                      left_context_size: Optional[int] = 128, right_context_size: Optional[int] = 128,
                      total_batch_duration: int = 1800, decoding_method: str = "ctc_greedy_search",
                      beam_size: int = 10, context_graph=None, return_nbest: bool = False,
+                     attn_weight: Optional[float] = None, search_ctc_weight: Optional[float] = None,
+                     search_transducer_weight: Optional[float] = None,
                      transducer_weight: Optional[float] = None, ctc_weight: Optional[float] = None,
                      reverse_weight: Optional[float] = None,
                      length_penalty: float = 0.0, max_len: Optional[int] = None):
@@ -641,12 +703,26 @@ class ChunkFormerModel:
         stopping at its own row count (or `max_len`); `beam_size` (1 .. 16), `length_penalty`.
         decoding_method "rnnt_beam_search" (transducer checkpoints): per masked batch one CTC log-softmax call
         (none at `ctc_weight` 0) and one transducer prefix beam search over the packed rows (transducer_beam.py;
-        `ctc_weight` default 0.3, `transducer_weight` default 0.7, `return_nbest` as for the CTC beam search)."""
+        `ctc_weight` default 0.3, `transducer_weight` default 0.7, `return_nbest` as for the CTC beam search).
+        decoding_method "rnnt_beam_attn_rescoring" (transducer checkpoints; transducer.py:257-391): the n-best of that
+        transducer beam search (`search_ctc_weight` default 0.3, `search_transducer_weight` default 0.7) re-ranked by
+        total = attn * `attn_weight` + search score * `ctc_weight` + td * `transducer_weight`, td the full-sum
+        transducer log-likelihood of the hypothesis (transducer_rescore.py, one device call per masked batch) and attn
+        the attention decoder's score (`reverse_weight` as in attention_rescoring).  `ctc_weight`, `transducer_weight`
+        and `attn_weight` default to 0.5 each, `attn_weight` to 0 when the checkpoint has no decoder: this project's
+        defaults -- the reference's CLI defaults are all 0, which always returns hypothesis 0.  `attn_weight` > 0
+        without a decoder is a ValueError.  With `return_nbest` the n-best comes back re-ranked by the totals.
+        decoding_method "ctc_beam_td_attn_rescoring": the same rescoring of the CTC prefix beam search's n-best
+        (`context_graph` honoured; the search score is the CTC prefix score).
+        `attn_weight`, `search_ctc_weight` and `search_transducer_weight` must be passed by keyword: they stand before
+        `transducer_weight` in the signature (its tail is kept as earlier callers know it), so positional arguments
+        past `return_nbest` are not a supported way to call this method."""
         self._require_asr("batch_decode")
         mode = self._resolve_decoding(decoding_method)
         opts = dict(beam_size=beam_size, context_graph=context_graph, return_nbest=return_nbest,
                     transducer_weight=transducer_weight, ctc_weight=ctc_weight, reverse_weight=reverse_weight,
-                    length_penalty=length_penalty, max_len=max_len)
+                    length_penalty=length_penalty, max_len=max_len, attn_weight=attn_weight,
+                    search_ctc_weight=search_ctc_weight, search_transducer_weight=search_transducer_weight)
         C = chunk_size if chunk_size is not None else 64
         L = left_context_size if left_context_size is not None else 128
         R = right_context_size if right_context_size is not None else 128
@@ -836,6 +912,24 @@ class ChunkFormerModel:
             pred, prob = self._classify_rows(eo.reshape(-1, eo.shape[-1]), starts, el)
             results.extend(self._label_dicts(pred, prob))
         return results
+
+
+def transducer_decoder_config(conf: dict, sd: Dict[str, torch.Tensor], vocab: int, d_model: int):
+    """The attention decoder of a `model: transducer` checkpoint for its rescoring modes: (AEDConfig, None) when the
+    checkpoint carries decoder.* tensors the rescorer can run, (None, reason) when it carries some it cannot (settings
+    AEDConfig.from_conf rejects, missing or mis-shaped tensors): the checkpoint then loads as it did without them and
+    the reason is raised when a rescoring mode asks for attn_weight > 0; (None, None) without decoder.* tensors."""
+    if not any(k.startswith("decoder.") for k in sd):
+        return None, None
+    try:
+        if conf.get("decoder", "transformer") not in ("transformer", "bitransformer"):
+            raise AssertionError(f"decoder: {conf.get('decoder')} is not transformer / bitransformer")
+        aed_cfg = AEDConfig.from_conf(conf, vocab, d_model)
+        from .rescore import native_names
+        native_names(aed_cfg, sd)
+        return aed_cfg, None
+    except (AssertionError, KeyError, ValueError) as e:
+        return None, str(e) or type(e).__name__
 
 
 def _cmvn_from_stats(mean_stat, var_stat, count):

@@ -377,7 +377,8 @@ cfm_status cfm_rnnt_greedy_ex(const cfm_rnnt* h, const float* enc_dev, int32_t r
  * "grid_blocks" = workgroups per utterance of the multi-CU search (default 32; 0 = one
  * workgroup per utterance always).  The multi-CU search runs when B <= 32 and B * grid_blocks <= the
  * device's CU count; cfm_rnnt_grid_blocks returns the workgroups per utterance a call with B
- * utterances uses (0: the one-workgroup kernel). */
+ * utterances uses (0: the one-workgroup kernel).  "lattice_dtype" (CFM_DTYPE_F32, the default, or CFM_DTYPE_BF16):
+ * the operand type of cfm_rnnt_td_score's joint lattice kernel for calls that pass dtype -1. */
 cfm_status cfm_rnnt_set_option(cfm_rnnt* h, const char* key, int64_t value);
 int32_t cfm_rnnt_grid_blocks(const cfm_rnnt* h, int32_t B);
 /* After a multi-CU call has completed: nonzero if one of its grid barriers timed out (the search then
@@ -411,6 +412,31 @@ cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc_dev, int32_t rows,
                                 int32_t* trace_parent, int32_t* trace_token, double* trace_score, float* trace_topv,
                                 int32_t* trace_topi, void* workspace, size_t workspace_bytes, cfm_stream stream);
 int32_t cfm_rnnt_beam_error(const void* workspace);
+
+/* ---- Full-sum transducer score of given hypotheses (the td score of the reference's modes rnnt_beam_attn_rescoring /
+ * ctc_beam_td_attn_rescoring: Transducer._cal_transducer_score = -rnnt_loss, transducer/transducer.py:257-391) over
+ * the same handle (csrc/rnnt_lattice.hip).  Hypothesis i of utterance utt (rows [row_start[utt], + row_len[utt]),
+ * T = row_len[utt] >= 1) with U tokens owns U + 1 predictor states and T * (U + 1) lattice nodes, node (t, u) at
+ * node0[i] + t * (U + 1) + u:
+ *   tokens_dev [n_states] int32: state u of hypothesis i at first_state + u holds the token the predictor consumed to
+ *     reach it (the blank for u = 0, y_u after); desc_dev [n_hyp][4] int32 = (utt, first_state, U + 1, 0);
+ *   node0_dev [n_hyp + 1] int64: the running sum of T * (U + 1), node0[n_hyp] = total_nodes; max_u1 >= every U + 1.
+ * One call = enc_ffn over the rows, max_u1 predictor steps over all hypotheses, the joint lattice kernel (per node
+ * only b = log p(blank) and k = log p(next token), f32; `dtype` selects exact f32 MFMA operands (CFM_DTYPE_F32) or
+ * bf16 operands with f32 accumulation (CFM_DTYPE_BF16), -1 the handle's "lattice_dtype" option, so that callers of
+ * different types share a handle without touching its state) and the f64 recursion
+ *   alpha[0,0] = 0, alpha[t,u] = log_add(alpha[t-1,u] + b[t-1,u], alpha[t,u-1] + k[t,u-1]),
+ *   td = alpha[T-1,U] + b[T-1,U]                                                       -> td_out [n_hyp] f64.
+ * Stream-ordered, no allocation after the handle's first call, no host synchronisation.  The first int32 of the
+ * workspace is a status word (cfm_rnnt_beam_error reads it): 0, 1 = a descriptor outside its arrays (that
+ * hypothesis' td is 0), 4 = a non-finite lattice node.  The workspace size is 0 for a geometry it cannot hold. */
+size_t cfm_rnnt_td_workspace_bytes(const cfm_rnnt* h, int32_t rows, int32_t n_hyp, int32_t n_states, int32_t max_u1,
+                                   int64_t total_nodes);
+cfm_status cfm_rnnt_td_score(cfm_rnnt* h, const float* enc_dev, int32_t rows, const int32_t* row_start_dev,
+                             const int32_t* row_len_dev, int32_t B, const int32_t* tokens_dev, int32_t n_states,
+                             const int32_t* desc_dev, const int64_t* node0_dev, int32_t n_hyp, int32_t max_u1,
+                             int64_t total_nodes, int32_t dtype, double* td_out, void* workspace,
+                             size_t workspace_bytes, cfm_stream stream);
 
 /* ---- classification consumer (model: classification checkpoints): masked mean pool over time of the
  * encoder output and the per-task linear heads, the reference's SpeechClassificationModel

@@ -112,6 +112,23 @@ cfm_status cfm_op_rnnt_lstm_step(cfm_rnnt* h, const int32_t* tokens, const float
                                  float* h_out, float* c_out, float* pred_out, void* workspace, size_t workspace_bytes,
                                  cfm_stream stream);
 
+/* The kernels of the full-sum transducer score (csrc/rnnt_lattice.hip, cfm_rnnt_td_score in cfm.h), one at a time.
+ * lattice: the joint over the lattice nodes of cfm_rnnt_td_score's descriptors from given projections: enc_proj
+ *   [rows, join_dim] f32 (enc_ffn with bias), pred_proj [n_states, join_dim] f32 (pred_ffn of the predictor output
+ *   of each state); per node b = log_softmax(ffn_out(tanh(e + p)))[blank] and k = the same at the next state's
+ *   token (0 on a hypothesis' last state) into b_out / k_out [total_nodes] f32.  dtype CFM_DTYPE_F32 / CFM_DTYPE_BF16.
+ * alpha: the recursion of cfm_rnnt_td_score on given b / k [total_nodes] f32: hypothesis i has hyp_t[i] frames and
+ *   hyp_u1[i] states, its nodes from node0[i] on -> td_out [n_hyp] f64; the first int32 of the workspace is the
+ *   status word (1 = a hypothesis outside b / k, its td 0; 4 = a non-finite node). */
+cfm_status cfm_op_rnnt_lattice(cfm_rnnt* h, int32_t dtype, const float* enc_proj, int32_t rows, const float* pred_proj,
+                               int32_t n_states, const int32_t* tokens, const int32_t* row_start,
+                               const int32_t* row_len, int32_t B, const int32_t* desc, const int64_t* node0,
+                               int32_t n_hyp, int64_t total_nodes, float* b_out, float* k_out, cfm_stream stream);
+size_t cfm_op_rnnt_alpha_workspace_bytes(int32_t n_hyp, int32_t max_u1);
+cfm_status cfm_op_rnnt_alpha(const float* b, const float* k, const int32_t* hyp_t, const int32_t* hyp_u1,
+                             const int64_t* node0, int32_t n_hyp, int32_t max_u1, int64_t total_nodes, double* td_out,
+                             void* workspace, size_t workspace_bytes, cfm_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
