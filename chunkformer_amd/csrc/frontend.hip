@@ -641,7 +641,8 @@ int frontend_conv0_dw(const float* feats, const float* const* tab, int step, con
       CFM_CHECK_LAUNCH();
       return 0;
     }
-    if (var >= 1 || std::is_same<T, bf16>::value)   // the position-stationary MFMA kernel (bf16: also at 0)
+    // the position-stationary MFMA kernel (bf16: also at 0); var < 0: the VALU kernel at any type (cfm_op_frontend_conv0_dw)
+    if (var >= 1 || (var == 0 && std::is_same<T, bf16>::value))
       hipLaunchKernelGGL(fe_conv0_dw_mfma_kernel<T>, dim3((T2 * FE_F2 + FE_POS_BLOCK - 1) / FE_POS_BLOCK, nwin), dim3(256),
                          0, st, feats, tab, step, meta, meta_stride, W, T2, cmvn_mean, cmvn_istd, wpack, d, out);
     else

@@ -1029,6 +1029,150 @@ cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const 
   return CFM_OK;
 }
 
+// the row-wise kernels of the encoder step, one at a time (include/cfm_ops.h)
+extern "C++" {
+namespace {
+template <typename T>
+int op_layernorm(int kind, float* x, int M, int d, const void* y, float alpha, const uint8_t* ymask, const void* y2,
+                 float alpha2, const uint8_t* ymask2, bool defer, const float* w1, const float* b1, const float* w2,
+                 const float* b2, float eps, void* out, const uint8_t* rowmask, hipStream_t st) {
+  cfm::ResidAdd<T> ra;
+  ra.y = (const T*)y; ra.alpha = alpha; ra.ymask = ymask;
+  ra.y2 = (const T*)y2; ra.alpha2 = alpha2; ra.ymask2 = ymask2; ra.defer = defer;
+  if (kind == CFM_LN) return cfm::layernorm<T>(x, ra, M, d, w1, b1, eps, (T*)out, rowmask, st);
+  if (kind == CFM_LN2) return cfm::layernorm2<T>(x, ra, M, d, w1, b1, w2, b2, eps, (T*)out, st);
+  return cfm::layernorm2_f32<T>(x, ra, M, d, w1, b1, w2, b2, eps, (float*)out, st);
+}
+bool op_dtype_ok(int32_t dtype) { return dtype == CFM_DTYPE_F32 || dtype == CFM_DTYPE_BF16 || dtype == CFM_DTYPE_F16; }
+}  // namespace
+}  // extern "C++"
+
+cfm_status cfm_op_layernorm(int32_t dtype, int32_t kind, float* x, int32_t M, int32_t d, const void* y, float alpha,
+                            const uint8_t* ymask, const void* y2, float alpha2, const uint8_t* ymask2, int32_t defer,
+                            const float* w1, const float* b1, const float* w2, const float* b2, float eps, void* out,
+                            const uint8_t* rowmask, cfm_stream stream) {
+  static const char* const KNAME[] = {"layernorm", "layernorm2", "layernorm2_f32"};
+  if (kind < CFM_LN || kind > CFM_LN2_F32) return set_error(CFM_ERR_VALUE, "layernorm: unknown kind");
+  if (!op_dtype_ok(dtype)) return set_error(CFM_ERR_VALUE, "layernorm: unknown dtype");
+  if (!x || !w1 || !b1 || !out || M < 0) return set_error(CFM_ERR_VALUE, "layernorm: null argument / M < 0");
+  if (!y && (y2 || ymask || ymask2 || defer))
+    return set_error(CFM_ERR_VALUE, "layernorm: y2 / ymask / ymask2 / defer need the first branch y");
+  if (!y2 && ymask2) return set_error(CFM_ERR_VALUE, "layernorm: ymask2 without y2");
+  if (kind != CFM_LN && (rowmask || defer))
+    return set_error(CFM_ERR_VALUE, "layernorm: rowmask and defer belong to the one-LayerNorm kernel");
+  if (w2 && !b2) return set_error(CFM_ERR_VALUE, "layernorm: w2 without b2");
+  if (d != 128 && d != 256 && d != 512)
+    return set_error(CFM_ERR_ASSERT, std::string("layernorm: the ") + KNAME[kind] + " kernel takes d = 128, 256 or 512");
+  hipStream_t st = (hipStream_t)stream;
+  int r;
+  if (dtype == CFM_DTYPE_F32)
+    r = op_layernorm<float>(kind, x, M, d, y, alpha, ymask, y2, alpha2, ymask2, defer != 0, w1, b1, w2, b2, eps, out, rowmask, st);
+  else if (dtype == CFM_DTYPE_F16)
+    r = op_layernorm<f16>(kind, x, M, d, y, alpha, ymask, y2, alpha2, ymask2, defer != 0, w1, b1, w2, b2, eps, out, rowmask, st);
+  else
+    r = op_layernorm<bf16>(kind, x, M, d, y, alpha, ymask, y2, alpha2, ymask2, defer != 0, w1, b1, w2, b2, eps, out, rowmask, st);
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string(KNAME[kind]) + ": " + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
+cfm_status cfm_op_conv_module(int32_t dtype, const void* glu, const int32_t* desc, int32_t nblk, int32_t d,
+                              const float* wdw_t, const float* bdw, const float* lnw, const float* lnb, float eps,
+                              void* out, cfm_stream stream) {
+  if (!op_dtype_ok(dtype)) return set_error(CFM_ERR_VALUE, "conv_module: unknown dtype");
+  if (!glu || !desc || !wdw_t || !bdw || !lnw || !lnb || !out || nblk < 0)
+    return set_error(CFM_ERR_VALUE, "conv_module: null argument / nblk < 0");
+  if (d != 128 && d != 256 && d != 512)
+    return set_error(CFM_ERR_ASSERT, "conv_module: the conv_dw_ln_silu kernels take d = 128, 256 or 512");
+  hipStream_t st = (hipStream_t)stream;
+  int r;
+  if (dtype == CFM_DTYPE_F32)
+    r = conv_dw_ln_silu<float>((const float*)glu, desc, nblk, d, wdw_t, bdw, lnw, lnb, eps, (float*)out, st);
+  else if (dtype == CFM_DTYPE_F16)
+    r = conv_dw_ln_silu<f16>((const f16*)glu, desc, nblk, d, wdw_t, bdw, lnw, lnb, eps, (f16*)out, st);
+  else
+    r = conv_dw_ln_silu<bf16>((const bf16*)glu, desc, nblk, d, wdw_t, bdw, lnw, lnb, eps, (bf16*)out, st);
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string("conv_dw_ln_silu: ") + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
+cfm_status cfm_op_pos_table(int32_t dtype, int32_t d, int32_t p_rows, int32_t anchor, void* out, cfm_stream stream) {
+  if (!op_dtype_ok(dtype)) return set_error(CFM_ERR_VALUE, "pos_table: unknown dtype");
+  if (!out || p_rows < 0) return set_error(CFM_ERR_VALUE, "pos_table: null argument / p_rows < 0");
+  if (d <= 0 || d % 2) return set_error(CFM_ERR_ASSERT, "pos_table: the pos_table kernel takes an even d");
+  hipStream_t st = (hipStream_t)stream;
+  int r;
+  if (dtype == CFM_DTYPE_F32) r = pos_table<float>(d, p_rows, anchor, (float*)out, st);
+  else if (dtype == CFM_DTYPE_F16) r = pos_table<f16>(d, p_rows, anchor, (f16*)out, st);
+  else r = pos_table<bf16>(d, p_rows, anchor, (bf16*)out, st);
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string("pos_table: ") + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
+// the front-end kernels on a model's own weights (include/cfm_ops.h)
+cfm_status cfm_op_frontend_conv0_dw(const cfm_model* m, int32_t kernel, int32_t k, int32_t use_cmvn, const float* feats,
+                                    const float* const* tab, int32_t step, const int32_t* meta, int32_t nwin, int32_t W,
+                                    void* out, cfm_stream stream) {
+  static const char* const KNAME[] = {"fe_conv0_dw (VALU)", "fe_conv0_dw_mfma (position-stationary)",
+                                      "fe_conv0_dw_mfma2 (channel-stationary)"};
+  if (!m || !meta || !out || (!feats && !tab)) return set_error(CFM_ERR_VALUE, "frontend_conv0_dw: null argument");
+  if (kernel < CFM_FE_VALU || kernel > CFM_FE_MFMA_CH || k < 0 || nwin < 0)
+    return set_error(CFM_ERR_VALUE, "frontend_conv0_dw: unknown kernel / k < 0 / nwin < 0");
+  const int d = m->cfg.d_model, dt = m->cfg.compute_dtype;
+  const int T1 = (W - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1;
+  if (W < 7 || T2 <= 0) return set_error(CFM_ERR_VALUE, "frontend_conv0_dw: W < 7");
+  const FrontW& F = m->fe;
+  bool takes = true;
+  if (kernel != CFM_FE_VALU)   // the MFMA kernels: 16-bit models, 64-channel store passes, 32-bit output offsets
+    takes = dt != CFM_DTYPE_F32 && d % 64 == 0 && (size_t)T2 * 19 * d * 2 < ((size_t)1 << 31);
+  if (kernel == CFM_FE_MFMA_CH && !F.wfrag) takes = false;
+  if (!takes)
+    return set_error(CFM_ERR_ASSERT, std::string("frontend_conv0_dw: the ") + KNAME[kernel] + " kernel does not take this model (dtype, d)");
+  HIPC(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)stream;
+  const float *cm = use_cmvn ? F.cm : nullptr, *ci = use_cmvn ? F.ci : nullptr;
+  if (use_cmvn && !cm) return set_error(CFM_ERR_VALUE, "frontend_conv0_dw: use_cmvn on a model without CMVN");
+  const int var = kernel == CFM_FE_VALU ? -1 : kernel == CFM_FE_MFMA_POS ? 1 : 2 + k;
+  int r;
+  if (dt == CFM_DTYPE_F32)
+    r = frontend_conv0_dw<float>(feats, tab, step, meta, PLAN_REC, nwin, W, cm, ci, F.w0, F.b0, F.w1, F.b1, F.wpack, F.wfrag, d, (float*)out, st, var);
+  else if (dt == CFM_DTYPE_F16)
+    r = frontend_conv0_dw<f16>(feats, tab, step, meta, PLAN_REC, nwin, W, cm, ci, F.w0, F.b0, F.w1, F.b1, F.wpack, F.wfrag, d, (f16*)out, st, var);
+  else
+    r = frontend_conv0_dw<bf16>(feats, tab, step, meta, PLAN_REC, nwin, W, cm, ci, F.w0, F.b0, F.w1, F.b1, F.wpack, F.wfrag, d, (bf16*)out, st, var);
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string("frontend_conv0_dw (") + KNAME[kernel] + "): " + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
+cfm_status cfm_op_frontend_dw2(const cfm_model* m, int32_t mode, const void* in, int32_t nwin, int32_t T2, int32_t seg,
+                               void* out, cfm_stream stream) {
+  if (!m || !in || !out) return set_error(CFM_ERR_VALUE, "frontend_dw2: null argument");
+  if (mode != CFM_FE_DW2_UNFUSED && mode != CFM_FE_DW2_FUSED) return set_error(CFM_ERR_VALUE, "frontend_dw2: unknown mode");
+  if (nwin <= 0 || T2 < 3) return set_error(CFM_ERR_VALUE, "frontend_dw2: nwin <= 0 / T2 < 3");
+  const int d = m->cfg.d_model, dt = m->cfg.compute_dtype, T3 = (T2 - 3) / 2 + 1;
+  const FrontW& F = m->fe;
+  HIPC(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)stream;
+  int r;
+  if (mode == CFM_FE_DW2_FUSED) {
+    r = -1;
+    if (dt != CFM_DTYPE_F32) {   // the launch of ModelT::encode, at the default tuning
+      EpiArgs ef; ef.bias = F.b_pw1; ef.out = out; ef.ldo = d;
+      ef.dw_w = F.w2; ef.dw_b = F.b2; ef.t2n = T2; ef.t3n = T3; ef.f16 = dt == CFM_DTYPE_F16;
+      r = gemm_bf16_wst(EPI_DW2, ACT_RELU, (const bf16*)in, d, (const bf16*)F.pw1, d, nwin * T2 * 19, d, d, ef, st);
+    }
+    if (r == -1)
+      return set_error(CFM_ERR_ASSERT, "frontend_dw2: the fused pw1 + dw2 kernel (gemm_bf16_wst, EPI_DW2) does not take this model (dtype, d)");
+  } else if (dt == CFM_DTYPE_F32) {
+    r = frontend_dw2<float>((const float*)in, nwin, T2, d, F.w2, F.b2, (float*)out, st, seg);
+  } else if (dt == CFM_DTYPE_F16) {
+    r = frontend_dw2<f16>((const f16*)in, nwin, T2, d, F.w2, F.b2, (f16*)out, st, seg);
+  } else {
+    r = frontend_dw2<bf16>((const bf16*)in, nwin, T2, d, F.w2, F.b2, (bf16*)out, st, seg);
+  }
+  if (r) return set_error(CFM_ERR_RUNTIME, std::string("frontend_dw2: ") + hipGetErrorString((hipError_t)r));
+  return CFM_OK;
+}
+
 size_t cfm_ctc_workspace_bytes(const cfm_model* m, int32_t rows) { return m ? m->ctc_ws_bytes(rows) : 0; }
 
 cfm_status cfm_ctc_logprobs(const cfm_model* m, const float* enc, int32_t rows, float* logp, int32_t* ids, void* ws,

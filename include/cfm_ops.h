@@ -56,6 +56,79 @@ cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const 
                             int32_t n_desc, int32_t H, int32_t dk, int32_t C, int32_t W, void* out, int32_t min_chunks,
                             void* vt, int32_t vt_ld, int32_t nutt, int32_t nd, int32_t t_keys, cfm_stream stream);
 
+/* One LayerNorm kernel on caller-owned buffers (csrc/norm.hip).  `kind` names the kernel and nothing else runs in
+ * its place: a d the kernels do not take (not 128 / 256 / 512) launches nothing, leaves x and out untouched and
+ * returns CFM_ERR_ASSERT naming the kernel; an argument combination outside the contract below is CFM_ERR_VALUE.
+ *   x [M][d] f32, read and written; y, y2 [M][d] dtype elements or null; ymask, ymask2, rowmask [M] bytes (0 / 1) or
+ *   null (= all 1); w1, b1, w2, b2 [d] f32.  Per row r, in f32 and in this order:
+ *     v = x_r;  if y: v = fmaf(alpha * ymask[r], y_r, v);  if y2 (needs y): v = fmaf(alpha2 * ymask2[r], y2_r, v)
+ *     LN(v; w, b) = (v - mean(v)) * rsqrt(mean((v - mean(v))^2) + eps) * w + b     (biased variance)
+ *   LN  (ln_kernel):      with y and not defer: x_r = v; with defer: x is left unwritten (the next LayerNorm
+ *                         re-applies the branch as its first term).  out_r = LN(v; w1, b1) as dtype, or a zero row
+ *                         where rowmask[r] == 0.  w2 / b2 are unused.
+ *   LN2 (ln2_kernel):     x_r = t = LN(v; w1, b1) (f32);  out_r = (w2 ? LN(t; w2, b2) : t) as dtype.
+ *   LN2_F32 (ln2_kernel): the same with out [M][d] f32.  defer and rowmask belong to LN alone. */
+typedef enum { CFM_LN = 0, CFM_LN2 = 1, CFM_LN2_F32 = 2 } cfm_ln_kind;
+cfm_status cfm_op_layernorm(int32_t dtype, int32_t kind, float* x, int32_t M, int32_t d, const void* y, float alpha,
+                            const uint8_t* ymask, const void* y2, float alpha2, const uint8_t* ymask2, int32_t defer,
+                            const float* w1, const float* b1, const float* w2, const float* b2, float eps, void* out,
+                            const uint8_t* rowmask, cfm_stream stream);
+
+/* The conv module's middle kernel (csrc/conv_module.hip, conv_dw_ln_silu<T>) on caller-owned buffers: depthwise conv
+ * k = 15 + bias, LayerNorm over the channels, SiLU.  dtype selects the kernel together with d: f32 the per-tap kernel,
+ * bf16 / f16 the dot2 whole-chunk kernel at d = 128 / 256 and the dot2 half-chunk kernel at d = 512; another d
+ * launches nothing, leaves out untouched and returns CFM_ERR_ASSERT naming the kernels.
+ *   glu, out: rows of d dtype elements; wdw_t [15][d] f32 tap-major; bdw, lnw, lnb [d] f32;
+ *   desc [nblk][8] int32 on the device: (OUT_ROW0, NOUT <= 64, SRC_ROW0, J_LO, J_HI, -, -, -).  For block b, i < NOUT:
+ *     a_c = bdw_c + sum over t < 15 with J_LO <= i + t < J_HI of wdw_t[t][c] * glu[SRC_ROW0 + i + t][c]
+ *     out[OUT_ROW0 + i] = silu(LN(a; lnw, lnb, eps))
+ *   glu rows of columns outside [J_LO, J_HI) are never read (SRC_ROW0 and J_LO may be negative); the 16-bit kernels
+ *   run the conv on taps rounded to dtype.  Rows no block covers are not written. */
+cfm_status cfm_op_conv_module(int32_t dtype, const void* glu, const int32_t* desc, int32_t nblk, int32_t d,
+                              const float* wdw_t, const float* bdw, const float* lnw, const float* lnb, float eps,
+                              void* out, cfm_stream stream);
+
+/* The relative-position table kernel (csrc/misc.hip, pos_table_kernel): out [p_rows][d] dtype elements, row k at
+ * distance p = anchor - k: out[k][2i] = sin(p * div_i), out[k][2i + 1] = cos(p * div_i), div_i = exp(2i * -(ln 1e4 / d)),
+ * the angle |p| * div_i formed in f32.  d must be even (CFM_ERR_ASSERT otherwise, nothing launched). */
+cfm_status cfm_op_pos_table(int32_t dtype, int32_t d, int32_t p_rows, int32_t anchor, void* out, cfm_stream stream);
+
+/* One front-end conv0 + ReLU + dw1 kernel (csrc/frontend.hip) on a model's own weights (w0, b0, w1, b1, the packed
+ * MFMA operands and CMVN of `m`; the element type is the model's compute dtype).  `kernel` names the kernel and
+ * nothing else runs in its place -- in particular VALU on a bf16 model runs the VALU kernel, which the model's own
+ * "fe_conv" 0 does not: a (dtype, d) the selected kernel does not take launches nothing, leaves out untouched and
+ * returns CFM_ERR_ASSERT naming the kernel.
+ *   VALU:     fe_conv0_dw_kernel, any dtype: f32 arithmetic throughout, out rounded to the dtype.
+ *   MFMA_POS: fe_conv0_dw_mfma_kernel (position-stationary; "fe_conv" 1), bf16 / f16, d % 64 == 0: the input after
+ *             CMVN, w0 and b0 rounded to the dtype, conv0 accumulated in f32, ReLU and dw1 (w1, b1) in f32.
+ *   MFMA_CH:  fe_conv0_dw_mfma2_kernel (channel-stationary; "fe_conv" 2 + k: about k + 1 chunks of 256 dw1 positions
+ *             per workgroup), bf16 / f16, d % 64 == 0: as MFMA_POS, and conv0's ReLU output and w1 rounded to the
+ *             dtype as well (dw1 on MFMA; b1 f32).  k is ignored by the other kernels.
+ *   meta [nwin][8] int32 on the device, the plan's window records: window n reads W feature rows of 80 f32 from
+ *   feats + meta[n][0] * 80 (packed mode, tab null) or from tab[meta[n][6]] + meta[n][7] * step * 80 (table mode:
+ *   tab = device array of per-utterance row pointers); rows at or past meta[n][1] (NVALID) are zero padding and are
+ *   never read.  CMVN, (x - mean) * istd, is applied after the padding when use_cmvn (padding rows become
+ *   -mean * istd); with use_cmvn 0 it is skipped even if the model has CMVN.
+ *   out [nwin][T2][19][d], T1 = (W - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1:
+ *     out[n][t2][f2][c] = b1[c] + sum_{u,v<3} w1[c][u][v] * relu(b0[c] + sum_{a,b<3} w0[c][a][b] * x[4 t2 + 2u + a][4 f2 + 2v + b]) */
+typedef enum { CFM_FE_VALU = 0, CFM_FE_MFMA_POS = 1, CFM_FE_MFMA_CH = 2 } cfm_fe_kernel;
+cfm_status cfm_op_frontend_conv0_dw(const cfm_model* m, int32_t kernel, int32_t k, int32_t use_cmvn, const float* feats,
+                                    const float* const* tab, int32_t step, const int32_t* meta, int32_t nwin, int32_t W,
+                                    void* out, cfm_stream stream);
+
+/* The front-end's dw2 (depthwise 3x3, stride 2, + bias) on a model's own weights, in [nwin][T2][19][d] ->
+ * out [nwin][T3][9][d], T3 = (T2 - 3) / 2 + 1 (T2 >= 3), elements of the model's compute dtype:
+ *   UNFUSED: fe_dw2_kernel (csrc/frontend.hip) with `seg` row segments per walk; `in` is the pw1 + ReLU output:
+ *            out[n][t3][f3][c] = b2[c] + sum_{u,v<3} w2[c][u][v] * in[n][2 t3 + u][2 f3 + v][c]
+ *            (16-bit models: the 9 taps rounded to the dtype, f32 accumulation).
+ *   FUSED:   the pw1 + ReLU + dw2 weight-stationary GEMM (csrc/gemm_wst_impl.h, EPI_DW2) with the model's pw1, b_pw1,
+ *            w2, b2; `in` is the dw1 output and the pw1 rows relu(in . pw1^T + b_pw1), rounded to the dtype, never
+ *            reach memory.  Where gemm_bf16_wst declines (an fp32 model, d != 512) nothing is launched, out is left
+ *            untouched and the call returns CFM_ERR_ASSERT naming the kernel; `seg` is unused. */
+typedef enum { CFM_FE_DW2_UNFUSED = 0, CFM_FE_DW2_FUSED = 1 } cfm_fe_dw2_mode;
+cfm_status cfm_op_frontend_dw2(const cfm_model* m, int32_t mode, const void* in, int32_t nwin, int32_t T2, int32_t seg,
+                               void* out, cfm_stream stream);
+
 /* One segment attention kernel of the attention decoder on caller-owned buffers (csrc/aed.hip).  `kernel` names the
  * kernel and nothing else runs in its place: a configuration the selected kernel does not take launches nothing,
  * leaves `out` untouched and returns CFM_ERR_ASSERT naming the kernel.
