@@ -168,6 +168,8 @@ cfm_op_decode_attention = _sig("cfm_op_decode_attention", I32, I32, I32, P, P, I
 cfm_op_seg_attention = _sig("cfm_op_seg_attention", I32, I32, I32, P, I32, P, I32, P, I32, I32, I32, P, P, P)
 cfm_op_gemm = _sig("cfm_op_gemm", I32, I32, I32, I32, P, I32, P, I32, I32, I32, I32, P, ctypes.c_float, P, I32, I32, P,
                    I32, P, I32, P, I32, P)
+GEMM_NONE, GEMM_128, GEMM_256, GEMM_WST = 0, 1, 2, 3
+cfm_op_gemm_route = _sig("cfm_op_gemm_route", I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32)
 ATTN_GENERIC, ATTN_RING, ATTN_A128, ATTN_DENSE = 0, 1, 2, 3
 cfm_op_attention = _sig("cfm_op_attention", I32, I32, I32, P, P, I32, P, I32, I32, P, P, P, I32, I32, I32, I32, I32, P,
                         I32, P, I32, I32, I32, I32, P)
@@ -188,7 +190,7 @@ cfm_op_rnnt_lstm_step = _sig("cfm_op_rnnt_lstm_step", I32, P, P, P, P, I32, P, P
 cfm_op_rnnt_lattice = _sig("cfm_op_rnnt_lattice", I32, P, I32, P, I32, P, I32, P, P, P, I32, P, P, I32, I64, P, P, P)
 cfm_op_rnnt_alpha_workspace_bytes = _sig("cfm_op_rnnt_alpha_workspace_bytes", SZ, I32, I32)
 cfm_op_rnnt_alpha = _sig("cfm_op_rnnt_alpha", I32, P, P, P, P, P, I32, I32, I64, P, P, SZ, P)
-EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_attention", "cfm_op_layernorm", "cfm_op_conv_module", "cfm_op_pos_table",
+EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_gemm_route", "cfm_op_attention", "cfm_op_layernorm", "cfm_op_conv_module", "cfm_op_pos_table",
                 "cfm_op_frontend_conv0_dw", "cfm_op_frontend_dw2", "cfm_op_seg_attention", "cfm_op_decode_attention",
                 "cfm_op_rnnt_fused_topk", "cfm_op_rnnt_beam_prune_workspace_bytes", "cfm_op_rnnt_beam_prune",
                 "cfm_op_rnnt_lstm_step_workspace_bytes", "cfm_op_rnnt_lstm_step",

@@ -52,6 +52,80 @@ struct EpiArgs {
 int gemm_bf16_wst(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
                   const EpiArgs& ep, hipStream_t st);
 
+// ---- which kernel a projection GEMM runs on: host-only predicates (no device, no HIP call), shared by the
+// dispatchers (gemm, gemm_bf16_256, gemm_bf16_wst) and the route query of cfm_ops.h, so the two cannot drift
+enum { GEMM_ROUTE_NONE = 0, GEMM_ROUTE_128 = 1, GEMM_ROUTE_256 = 2, GEMM_ROUTE_WST = 3 };
+constexpr int GEMM_WST_K = 512;    // the weight-stationary kernel's K
+constexpr int GEMM_WST_MT = 64;    // and its rows per tile
+inline bool gemm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// The 256 x 256 and weight-stationary epilogues store 16 B per lane (gemm_bf16_epi.h store_pair16 /
+// wave_epilogue_fullrow: 8 16-bit columns at row * ld + 8 c; wave_epilogue: f32x4 at row * ld + 4 c; the
+// buffer stores of gemm_wst_impl.h likewise): every row pitch they write must keep those 16-B aligned, and so
+// must the base pointers.  QKV rows have pitch d (q) and 2 d (K | V stream), its 32-column store spans must not
+// straddle a q / K / V or head boundary.
+inline bool gemm_vec_epilogue_ok(int epi, int N, const EpiArgs& ep) {
+  switch (epi) {
+    case EPI_STORE:
+    case EPI_GLU:
+    case EPI_DW2: return ep.ldo % 8 == 0 && gemm_aligned16(ep.out);
+    case EPI_STORE_F32: return ep.ldo % 4 == 0 && gemm_aligned16(ep.out);
+    case EPI_RESID: return ep.ldx % 4 == 0 && gemm_aligned16(ep.x);
+    case EPI_QKV:
+      return ep.d > 0 && ep.d % 64 == 0 && N == 3 * ep.d && (ep.dk == 64 || ep.dk == 128) && ep.d % ep.dk == 0 &&
+             gemm_aligned16(ep.out) && gemm_aligned16(ep.out2);
+  }
+  return false;
+}
+// K = 512 weight-stationary kernel (gemm_wst_impl.h); 16-bit operands only (the caller checks the type)
+inline bool gemm_wst_eligible(int epi, int act, int lda, int ldw, int M, int N, int K, const EpiArgs& ep) {
+  if (K != GEMM_WST_K || N <= 0 || N % 256 || lda % 8 || ldw % 8 || M <= 0) return false;
+  // enough row tiles for every CU of an XCD's column tiles to own some: 512 for the GLU epilogue,
+  // 128 otherwise (measured at endless_decode's 12.7k-row segments: FFN w1 45 -> 41 us, QKV 36 ->
+  // 30 us; GLU 20 -> 24 us, so it keeps the 256 x 256 kernel there); ep.wst == 2: any M (A/B)
+  const int min_tiles = epi == EPI_GLU ? 512 : 128;
+  if (ep.wst < 2 && epi != EPI_DW2 && (M + GEMM_WST_MT - 1) / GEMM_WST_MT < min_tiles) return false;
+  if (N / 256 > 32) return false;
+  if (!gemm_vec_epilogue_ok(epi, N, ep)) return false;
+  switch (epi) {
+    case EPI_STORE:
+    case EPI_QKV: return true;
+    case EPI_GLU: return ep.bias != nullptr;
+    case EPI_DW2:   // front-end pw1 + ReLU + dw2 (N = 512, dw2 taps / bias / geometry in ep; bf16 or f16)
+      return act == ACT_RELU && N == 512 && ep.dw_w && ep.dw_b && ep.t2n >= 3;
+  }
+  return false;
+}
+// 256 x 256 persistent LDS-DMA kernel (gemm_bf16.hip); 16-bit operands only
+inline bool gemm_256_eligible(int epi, int act, int lda, int ldw, int M, int N, int K, const EpiArgs& ep) {
+  (void)act;
+  if (M <= 0 || N <= 0 || K <= 0 || N % 256 || K % 64 || lda % 8 || ldw % 8) return false;
+  if (((M + 255) / 256) * (N / 256) < ep.big_min_tiles) return false;   // too few tiles to fill the chip
+  if (epi < EPI_STORE || epi > EPI_GLU) return false;
+  if (epi == EPI_GLU && ep.bias == nullptr) return false;
+  return gemm_vec_epilogue_ok(epi, N, ep);
+}
+// 128 x 128 kernel (gemm.hip), elements of esize bytes: 16-B operand loads (K step and row pitches in 16-B
+// chunks), scalar stores at any output pitch.  GLU pairs 16-column blocks and reads both biases; QKV splits
+// the columns at d and 2 d.
+inline bool gemm_128_eligible(int esize, int epi, int act, int lda, int ldw, int M, int N, int K, const EpiArgs& ep) {
+  (void)act;
+  const int epc = 16 / esize;
+  if (M <= 0 || N <= 0 || K <= 0 || K % (8 * epc) || lda % epc || ldw % epc) return false;
+  if (epi < EPI_STORE || epi > EPI_GLU) return false;
+  if (epi == EPI_GLU && (ep.bias == nullptr || N % 32)) return false;
+  if (epi == EPI_QKV && (ep.d <= 0 || N != 3 * ep.d || (ep.dk != 64 && ep.dk != 128) || ep.d % ep.dk)) return false;
+  return true;
+}
+// the kernel gemm<T> launches (sizeof(T) = esize); GEMM_ROUTE_NONE: nothing (an empty problem, or an error)
+inline int gemm_route(int esize, int epi, int act, int lda, int ldw, int M, int N, int K, const EpiArgs& ep) {
+  if (M <= 0 || N <= 0) return GEMM_ROUTE_NONE;
+  if (esize == 2 && !ep.small_tiles) {
+    if (ep.wst && gemm_wst_eligible(epi, act, lda, ldw, M, N, K, ep)) return GEMM_ROUTE_WST;
+    if (gemm_256_eligible(epi, act, lda, ldw, M, N, K, ep)) return GEMM_ROUTE_256;
+  }
+  return gemm_128_eligible(esize, epi, act, lda, ldw, M, N, K, ep) ? GEMM_ROUTE_128 : GEMM_ROUTE_NONE;
+}
+
 enum { SITE_QKV = 1, SITE_OPROJ = 2, SITE_PW2 = 4, SITE_FFN2 = 8, SITE_FFN1 = 16, SITE_PW1 = 32, SITE_FE = 64 };
 
 // Per-model kernel tuning (cfm_model_set_option); the defaults are the measured best
@@ -90,8 +164,9 @@ int gemm(int epi, int act, const T* A, int lda, const T* W, int ldw, int M, int 
 
 // A vocabulary projection (the CTC head, the attention decoders' output layer): out[rows, V] f32 (row pitch ldo) =
 // A[rows, d] . W[V, d]^T + bias.  The vocabulary splits into a 256-multiple part (256 x 256 MFMA tiles) and a
-// remainder (128 x 128 tiles); f32x4 epilogue stores need the row pitch V % 4 == 0.  `tuned`: the caller's kernel
-// selection, if it has one.
+// remainder (128 x 128 tiles); f32x4 epilogue stores need the row pitch V % 4 == 0 (gemm_vec_epilogue_ok checks the
+// pitch and the pointer again: a slab the rule below let through unaligned would run on 128 x 128 tiles).  `tuned`:
+// the caller's kernel selection, if it has one.
 template <typename T>
 inline int vocab_logits(const T* A, int rows, const T* W, const float* bias, int V, int d, float* out, int ldo,
                         hipStream_t st, const EpiArgs& tuned = EpiArgs()) {

@@ -192,29 +192,34 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const T* __restrict__ A, i
 template <typename T, int EPI, int ACT>
 static int launch(const T* A, int lda, const T* W, int ldw, int M, int N, int K, const EpiArgs& ep,
                   hipStream_t st) {
-  if (M <= 0 || N <= 0) return 0;
-  if (K % GemmTraits<T>::BK) return (int)hipErrorInvalidValue;
   const int nwg = ((M + 127) / 128) * ((N + 127) / 128);
   hipLaunchKernelGGL((gemm_kernel<T, EPI, ACT>), dim3(nwg), dim3(256), 0, st, A, lda, W, ldw, M, N, K, ep);
   CFM_CHECK_LAUNCH();
   return 0;
 }
 
-int gemm_bf16_big(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
+int gemm_bf16_256(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
                   const EpiArgs& ep, hipStream_t st);
 
+// One dispatcher: gemm_route (cfm_kernels.h) names the kernel, the launchers below re-check their own predicate
 template <typename T>
 int gemm(int epi, int act, const T* A, int lda, const T* W, int ldw, int M, int N, int K, const EpiArgs& ep,
          hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {   // bf16 / f16: the 256 x 256 and weight-stationary kernels (EpiArgs::f16)
-    if (!ep.small_tiles) {
-      EpiArgs e = ep;
-      e.f16 = std::is_same<T, f16>::value;
-      const int r = gemm_bf16_big(epi, act, reinterpret_cast<const bf16*>(A), lda, reinterpret_cast<const bf16*>(W),
-                                  ldw, M, N, K, e, st);
-      if (r != -1) return r;
+  if (M <= 0 || N <= 0) return 0;
+  EpiArgs e = ep;
+  e.f16 = std::is_same<T, f16>::value;   // bf16 / f16: the 256 x 256 and weight-stationary kernels (EpiArgs::f16)
+  const int route = gemm_route((int)sizeof(T), epi, act, lda, ldw, M, N, K, e);
+  if constexpr (sizeof(T) == 2) {
+    if (route == GEMM_ROUTE_WST || route == GEMM_ROUTE_256) {
+      const bf16* A16 = reinterpret_cast<const bf16*>(A);
+      const bf16* W16 = reinterpret_cast<const bf16*>(W);
+      // K = 512: weight tile in registers; else 256 x 256 tiles
+      const int r = route == GEMM_ROUTE_WST ? gemm_bf16_wst(epi, act, A16, lda, W16, ldw, M, N, K, e, st)
+                                            : gemm_bf16_256(epi, act, A16, lda, W16, ldw, M, N, K, e, st);
+      return r == -1 ? (int)hipErrorInvalidValue : r;
     }
   }
+  if (route != GEMM_ROUTE_128) return (int)hipErrorInvalidValue;
   switch (epi) {
     case EPI_STORE:
       if (act == ACT_RELU) return launch<T, EPI_STORE, ACT_RELU>(A, lda, W, ldw, M, N, K, ep, st);

@@ -242,20 +242,10 @@ static int launch256(const bf16* A, int lda, const bf16* W, int ldw, int M, int 
   return 0;
 }
 
-// returns -1 when the shape is not eligible (caller falls back to the 128x128 kernel)
-int gemm_bf16_wst(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
-                  const EpiArgs& ep, hipStream_t st);
-
-int gemm_bf16_big(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
+// returns -1 when the call is not eligible (gemm_256_eligible, cfm_kernels.h)
+int gemm_bf16_256(int epi, int act, const bf16* A, int lda, const bf16* W, int ldw, int M, int N, int K,
                   const EpiArgs& ep, hipStream_t st) {
-  if (M <= 0) return 0;
-  if (ep.wst) {
-    const int r = gemm_bf16_wst(epi, act, A, lda, W, ldw, M, N, K, ep, st);   // K = 512: weight tile in registers
-    if (r != -1) return r;
-  }
-  if (N % 256 || K % 64 || lda % 8 || ldw % 8) return -1;
-  if (((M + 255) / 256) * (N / 256) < ep.big_min_tiles) return -1;   // too few tiles to fill the chip
-  if (epi == EPI_GLU && ep.bias == nullptr) return -1;
+  if (!gemm_256_eligible(epi, act, lda, ldw, M, N, K, ep)) return -1;
   switch (epi) {
     case EPI_STORE:
       if (act == ACT_RELU) return launch256<EPI_STORE, ACT_RELU>(A, lda, W, ldw, M, N, K, ep, st);

@@ -33,8 +33,8 @@
 namespace cfm {
 
 namespace {
-constexpr int WST_K = 512;
-constexpr int WST_MT = 64;              // rows per tile
+constexpr int WST_K = GEMM_WST_K;       // 512
+constexpr int WST_MT = GEMM_WST_MT;     // rows per tile (64)
 constexpr int WST_KS = 64;              // K per step
 constexpr int WST_NK = WST_K / WST_KS;  // 8 steps per tile
 constexpr int WST_SLOT = WST_MT * WST_KS * 2;   // 8 KiB

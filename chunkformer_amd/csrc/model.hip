@@ -959,15 +959,26 @@ int32_t cfm_profile_read(const cfm_model* m, const char** names, double* total_m
   return PC_N;
 }
 
-cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, int32_t lda, const void* W, int32_t ldw,
-                       int32_t M, int32_t N, int32_t K, const float* bias, float alpha, void* out, int32_t ldo,
-                       int32_t row_off, void* out2, int32_t d, float* x, int32_t ldx, const uint8_t* rowmask,
-                       int32_t variant, cfm_stream stream) {
+// EpiArgs of a cfm_op_gemm call: the one place the variant word (include/cfm_ops.h) is decoded
+static EpiArgs op_gemm_args(const float* bias, float alpha, void* out, int32_t ldo, int32_t row_off, void* out2, int32_t d,
+                            float* x, int32_t ldx, const uint8_t* rowmask, int32_t variant) {
   EpiArgs e;
   e.bias = bias; e.alpha = alpha; e.out = out; e.out2 = out2; e.ldo = ldo; e.row_off = row_off; e.x = x; e.ldx = ldx;
   e.rowmask = rowmask; e.d = d; e.small_tiles = variant & 1; e.diag = (variant >> 8) & 0xff;
   e.store_mode = (variant >> 16) & 3;
   if ((variant >> 18) & 7) e.wst = ((variant >> 18) & 7) == 7 ? 0 : (variant >> 18) & 7;
+  if ((variant >> 21) & 1) e.dk = 128;
+  e.col_group = (variant >> 22) & 3;
+  if (const int f = (variant >> 24) & 15) e.big_min_tiles = 1 << (2 * f);
+  return e;
+}
+static int op_gemm_esize(int32_t dtype) { return dtype == CFM_DTYPE_F32 ? 4 : 2; }
+
+cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, int32_t lda, const void* W, int32_t ldw,
+                       int32_t M, int32_t N, int32_t K, const float* bias, float alpha, void* out, int32_t ldo,
+                       int32_t row_off, void* out2, int32_t d, float* x, int32_t ldx, const uint8_t* rowmask,
+                       int32_t variant, cfm_stream stream) {
+  const EpiArgs e = op_gemm_args(bias, alpha, out, ldo, row_off, out2, d, x, ldx, rowmask, variant);
   int r;
   if (dtype == CFM_DTYPE_F32)
     r = gemm<float>(epi, act, (const float*)A, lda, (const float*)W, ldw, M, N, K, e, (hipStream_t)stream);
@@ -977,6 +988,14 @@ cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, i
     r = gemm<bf16>(epi, act, (const bf16*)A, lda, (const bf16*)W, ldw, M, N, K, e, (hipStream_t)stream);
   if (r) return set_error(CFM_ERR_RUNTIME, std::string("gemm: ") + hipGetErrorString((hipError_t)r));
   return CFM_OK;
+}
+
+int32_t cfm_op_gemm_route(int32_t dtype, int32_t epi, int32_t act, int32_t lda, int32_t ldw, int32_t M, int32_t N,
+                          int32_t K, int32_t has_bias, int32_t ldo, int32_t ldx, int32_t variant) {
+  // stand-ins for the buffers: 16-B aligned and non-null where the epilogue has one; QKV: d = N / 3
+  static float buf[4] __attribute__((aligned(16)));
+  const EpiArgs e = op_gemm_args(has_bias ? buf : nullptr, 1.f, buf, ldo, 0, buf, N / 3, buf, ldx, nullptr, variant);
+  return gemm_route(op_gemm_esize(dtype), epi, act, lda, ldw, M, N, K, e);
 }
 
 cfm_status cfm_op_attention(int32_t dtype, int32_t kernel, const void* q, const void* kv, int32_t kv_rows, const void* P,

@@ -27,11 +27,27 @@ typedef enum { CFM_ACT_NONE = 0, CFM_ACT_RELU = 1, CFM_ACT_SILU = 2 } cfm_act;
  * variant (A/B testing): bit 0 forces the 128x128 kernel; bits 8-15 select a timing diagnostic of
  * the bf16 kernels (1 no MFMA, 2 no DMA in the loop, 3 no epilogue, 5 no stores; 0 = normal; only
  * in a library built with -DCFM_GEMM_DIAG); bits 16-17 the bf16 store policy (2 = nt); bits 18-20 the
- * K = 512 weight-stationary kernel (0 = model default, 1 = on, 2 = on at any M, 7 = off). */
+ * K = 512 weight-stationary kernel (0 = model default, 1 = on, 2 = on at any M, 7 = off); bit 21 the QKV head dim
+ * (0 = 64, 1 = 128: the K | V stream column of K / V column cc is (cc / dk) * 2 dk + {0, dk} + cc % dk); bits 22-23
+ * the 256 x 256 kernel's column-group width ("col_group": tiles ordered group, row, column; 0 = all columns); bits
+ * 24-27 a field f: the 256 x 256 kernel only from 4^f tiles of 256 x 256 on (f = 0: always; f = 15: never).
+ * act: 0 none, 1 ReLU, 2 SiLU, 3 SiLU of a -log2(e)-prescaled input (STORE: a / (1 + 2^a); GLU: the gate half is
+ * prescaled, out = a / (1 + 2^gate)).  GLU needs a bias and N % 32 == 0, QKV N == 3 d and d % dk == 0.
+ * Kernels: f32 runs on 128 x 128 tiles (K % 32 == 0, lda, ldw % 4 == 0).  bf16 / f16 (K % 64 == 0, lda, ldw % 8 == 0)
+ * run the weight-stationary kernel (K == 512, N % 256 == 0, N <= 8192, STORE / QKV / GLU, from 128 row tiles of 64 on,
+ * GLU from 512), else the 256 x 256 kernel (N % 256 == 0), else 128 x 128 tiles.  The two big kernels store 16 B per
+ * lane and take a call only if every pitch they write keeps that aligned -- ldo % 8 == 0 for 16-bit outputs, ldo % 4
+ * == 0 / ldx % 4 == 0 for f32 outputs, out / out2 / x 16-B aligned (QKV: d % 64 == 0) -- otherwise the call runs on
+ * 128 x 128 tiles, whose stores are scalar.  A call no kernel takes launches nothing and returns CFM_ERR_RUNTIME. */
 cfm_status cfm_op_gemm(int32_t dtype, int32_t epi, int32_t act, const void* A, int32_t lda, const void* W, int32_t ldw,
                        int32_t M, int32_t N, int32_t K, const float* bias, float alpha, void* out, int32_t ldo,
                        int32_t row_off, void* out2, int32_t d, float* x, int32_t ldx, const uint8_t* rowmask,
                        int32_t variant, cfm_stream stream);
+/* The kernel the call above would launch, decided by the same host predicates as the launch itself; touches no
+ * device.  Buffers are taken as 16-B aligned (and d = N / 3 for QKV).  0 = none (an empty problem or an error). */
+typedef enum { CFM_GEMM_NONE = 0, CFM_GEMM_128 = 1, CFM_GEMM_256 = 2, CFM_GEMM_WST = 3 } cfm_gemm_route;
+int32_t cfm_op_gemm_route(int32_t dtype, int32_t epi, int32_t act, int32_t lda, int32_t ldw, int32_t M, int32_t N,
+                          int32_t K, int32_t has_bias, int32_t ldo, int32_t ldx, int32_t variant);
 
 /* One attention kernel on caller-owned buffers (csrc/attention.hip, attention128.hip).  `kernel` names the
  * kernel and nothing else runs in its place: when the selected kernel does not take the configuration
