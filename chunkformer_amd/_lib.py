@@ -112,6 +112,15 @@ class CfmRnntConfig(ctypes.Structure):
 
 cfm_rnnt_create = _sig("cfm_rnnt_create", I32, ctypes.POINTER(CfmRnntConfig), ctypes.POINTER(CfmTensorView), I32, I32,
                        ctypes.POINTER(P))
+
+
+class CfmRnntPredictorConfig(ctypes.Structure):
+    _fields_ = [("kind", I32), ("history_size", I32), ("n_head", I32), ("activation", I32), ("conv_bias", I32),
+                ("ln_eps", ctypes.c_float)]
+
+
+cfm_rnnt_create_ex = _sig("cfm_rnnt_create_ex", I32, ctypes.POINTER(CfmRnntConfig), ctypes.POINTER(CfmRnntPredictorConfig),
+                          ctypes.POINTER(CfmTensorView), I32, I32, ctypes.POINTER(P))
 cfm_rnnt_destroy = _sig("cfm_rnnt_destroy", None, P)
 cfm_rnnt_workspace_bytes = _sig("cfm_rnnt_workspace_bytes", SZ, P, I32)
 cfm_rnnt_greedy = _sig("cfm_rnnt_greedy", I32, P, P, I32, P, P, I32, I32, P, P, SZ, P)
@@ -187,6 +196,8 @@ cfm_op_rnnt_beam_prune_workspace_bytes = _sig("cfm_op_rnnt_beam_prune_workspace_
 cfm_op_rnnt_beam_prune = _sig("cfm_op_rnnt_beam_prune", I32, P, P, I32, I32, I32, P, P, P, P, P, SZ, P)
 cfm_op_rnnt_lstm_step_workspace_bytes = _sig("cfm_op_rnnt_lstm_step_workspace_bytes", SZ, P, I32)
 cfm_op_rnnt_lstm_step = _sig("cfm_op_rnnt_lstm_step", I32, P, P, P, P, I32, P, P, P, P, SZ, P)
+cfm_op_rnnt_predictor_step_workspace_bytes = _sig("cfm_op_rnnt_predictor_step_workspace_bytes", SZ, P, I32)
+cfm_op_rnnt_predictor_step = _sig("cfm_op_rnnt_predictor_step", I32, P, P, I32, P, P, P, SZ, P)
 cfm_op_rnnt_lattice = _sig("cfm_op_rnnt_lattice", I32, P, I32, P, I32, P, I32, P, P, P, I32, P, P, I32, I64, P, P, P)
 cfm_op_rnnt_alpha_workspace_bytes = _sig("cfm_op_rnnt_alpha_workspace_bytes", SZ, I32, I32)
 cfm_op_rnnt_alpha = _sig("cfm_op_rnnt_alpha", I32, P, P, P, P, P, I32, I32, I64, P, P, SZ, P)
@@ -194,6 +205,7 @@ EXPORTED_OPS = ["cfm_op_gemm", "cfm_op_gemm_route", "cfm_op_attention", "cfm_op_
                 "cfm_op_frontend_conv0_dw", "cfm_op_frontend_dw2", "cfm_op_seg_attention", "cfm_op_decode_attention",
                 "cfm_op_rnnt_fused_topk", "cfm_op_rnnt_beam_prune_workspace_bytes", "cfm_op_rnnt_beam_prune",
                 "cfm_op_rnnt_lstm_step_workspace_bytes", "cfm_op_rnnt_lstm_step",
+                "cfm_op_rnnt_predictor_step_workspace_bytes", "cfm_op_rnnt_predictor_step",
                 "cfm_op_rnnt_lattice", "cfm_op_rnnt_alpha_workspace_bytes", "cfm_op_rnnt_alpha"]
 
 EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_destroy", "cfm_model_set_option",
@@ -202,7 +214,7 @@ EXPORTED = ["cfm_version", "cfm_last_error", "cfm_model_create", "cfm_model_dest
             "cfm_ctc_logprobs", "cfm_ctc_ids_workspace_bytes", "cfm_ctc_ids", "cfm_ctc_collapse",
             "cfm_plan_stream", "cfm_workspace_bytes_stream", "cfm_encode_stream",
             "cfm_fbank_create", "cfm_fbank_destroy", "cfm_fbank_num_frames", "cfm_fbank_compute",
-            "cfm_rnnt_create", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
+            "cfm_rnnt_create", "cfm_rnnt_create_ex", "cfm_rnnt_destroy", "cfm_rnnt_workspace_bytes", "cfm_rnnt_greedy",
             "cfm_rnnt_greedy_ex", "cfm_rnnt_set_option", "cfm_rnnt_grid_blocks", "cfm_rnnt_error",
             "cfm_rnnt_beam_workspace_bytes", "cfm_rnnt_beam_search", "cfm_rnnt_beam_error",
             "cfm_rnnt_td_workspace_bytes", "cfm_rnnt_td_score",

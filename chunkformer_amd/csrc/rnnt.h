@@ -19,7 +19,24 @@ struct RnntDev {
   const float *wp, *bp;                   // [H, J], [J]: projection and pred_ffn composed (P = J)
   const float *wo, *bo;                   // [J, Vp] (zero-padded columns), [Vp] (padding -inf)
   int V, Vp, E, H, nl, P, J, blank;
+  // the stateless predictors (kind != CFM_RNNT_PRED_RNN: H = nl = 0, P = E, wp / bp = pred_ffn [E, J], [J])
+  int kind, Kc, act;                      // Kc = history_size + 1 ids of context
+  float ln_eps, mix_div;                  // embedding: n_head * Kc
+  const float* tap;                       // [Kc, E]: embedding q_c (pos_embed heads summed), conv the taps conv.weight[:, 0, c]
+  const float* cbias;                     // [E] conv.bias or null
+  const float *wf, *bf;                   // embedding: ffn [E, E] transposed, [E]
+  const float *gamma, *beta;              // norm [E]
 };
+
+// the stateless predictors' activation (CFM_RNNT_ACT_*; gelu is torch's default erf form)
+__device__ __forceinline__ float rnnt_act(int act, float v) {
+  switch (act) {
+    case CFM_RNNT_ACT_RELU: return v > 0.f ? v : 0.f;
+    case CFM_RNNT_ACT_SWISH: return v / (1.f + expf(-v));
+    case CFM_RNNT_ACT_TANH: return tanhf(v);
+    default: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+  }
+}
 
 struct RnntGrid {
   const float4* wg[RNNT_MAXL];  // per layer, block-major [K_l][n_b] slices of gate quads (i, f, g, o of a unit)
@@ -53,6 +70,8 @@ struct cfm_rnnt {
   void* beam_mem = nullptr;
   const float* bw_g[cfm::RNNT_MAXL] = {};
   const float *bw_p = nullptr, *bw_o = nullptr;
+  const float* bw_f = nullptr;                // stateless embedding predictor: ffn [E][E] (torch layout)
+  std::vector<float> host_wf;                 // its transposed image [E][E]
   // the lattice kernel's bf16 operand (rnnt_lattice.hip builds it on its first bf16 call, under lat_mu, from host_wo):
   // ffn_out as two bf16 images [2][V][J], hi and lo = bf16(w - hi); the f32 kernel reads bw_o
   std::mutex lat_mu;

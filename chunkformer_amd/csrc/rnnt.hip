@@ -17,6 +17,9 @@
 //          the sequential loop decides them, and the search resumes at that frame.
 //      Every loop iteration either advances the frame or counts an emission against the frame's
 //      n_steps budget, so the kernel ends after at most T * (n_steps + 1) iterations.
+//   A stateless handle (embedding / conv predictor, cfm_rnnt_create_ex) runs the same kernel with the predictor
+//   replaced by sl_predictor: the state is the window of the last K token ids, the predictor a gather of K
+//   embedding rows, their mix, (embedding) one E x E product, LayerNorm, the activation and the E x J pred_ffn.
 //   Matrix-vector products read transposed f32 weights [K][M] with one float4 of outputs per
 //   thread (coalesced rows, the input vector broadcast from LDS); argmax ties go to the lower id
 //   like torch.argmax.  Everything is f32 (log_softmax is monotone: argmax of the logits).
@@ -109,6 +112,66 @@ CFM_DEV void predictor(const RnntDev& w, int tok, const float* h, const float* c
   matvec(w.wp, H, w.J, xin, w.bp, pj, red, tid);   // composed projection + pred_ffn (cfm_rnnt_create)
 }
 
+// The stateless predictors (predictor.py:210-471) for the id window win[0 .. Kc) (oldest first, -1 = a position before
+// the sos: a zero vector): the Kc embedding rows into LDS, the mix (embedding: Kc dot products with the summed
+// pos_embed heads, the weighted sum of the rows and the E x E ffn; conv: the per-channel taps), LayerNorm, activation
+// and pj = pred_ffn(y).  sc: 32 floats of reductions.
+CFM_DEV void sl_predictor(const RnntDev& w, const int* win, float* rows, float* x, float* y, float* pj, float* red,
+                          float* sc, int tid) {
+  const int E = w.E, Kc = w.Kc, lane = tid & 63, wid = tid >> 6;
+  for (int e = tid; e < Kc * E; e += RNNT_NT) {
+    const int c = e / E, d = e - c * E, id = win[c];
+    rows[e] = id >= 0 ? w.embed[(size_t)id * E + d] : 0.f;
+  }
+  __syncthreads();
+  if (w.kind == CFM_RNNT_PRED_EMBEDDING) {
+    for (int c = wid; c < Kc; c += RNNT_NT / 64) {
+      float s = 0.f;
+      for (int d = lane; d < E; d += 64) s = fmaf(rows[c * E + d], w.tap[c * E + d], s);
+      s = wave_sum(s);
+      if (lane == 0) sc[c] = s;
+    }
+    __syncthreads();
+    for (int d = tid; d < E; d += RNNT_NT) {
+      float a = 0.f;
+      for (int c = 0; c < Kc; ++c) a = fmaf(sc[c], rows[c * E + d], a);
+      x[d] = a / w.mix_div;
+    }
+    __syncthreads();
+    matvec(w.wf, E, E, x, w.bf, y, red, tid);
+  } else {
+    for (int d = tid; d < E; d += RNNT_NT) {
+      float a = 0.f;
+      for (int c = 0; c < Kc; ++c) a = fmaf(w.tap[c * E + d], rows[c * E + d], a);
+      y[d] = w.cbias ? a + w.cbias[d] : a;
+    }
+    __syncthreads();
+  }
+  // LayerNorm (two passes, as torch: mean, then the variance about it) and the activation
+  float s = 0.f;
+  for (int d = tid; d < E; d += RNNT_NT) s += y[d];
+  s = wave_sum(s);
+  if (lane == 0) sc[16 + wid] = s;
+  __syncthreads();
+  float mean = 0.f;
+  for (int q = 0; q < RNNT_NT / 64; ++q) mean += sc[16 + q];
+  mean /= (float)E;
+  float v = 0.f;
+  for (int d = tid; d < E; d += RNNT_NT) { const float dd = y[d] - mean; v = fmaf(dd, dd, v); }
+  v = wave_sum(v);
+  if (lane == 0) sc[24 + wid] = v;
+  __syncthreads();
+  float var = 0.f;
+  for (int q = 0; q < RNNT_NT / 64; ++q) var += sc[24 + q];
+  const float rstd = 1.f / sqrtf(var / (float)E + w.ln_eps);
+  for (int d = tid; d < E; d += RNNT_NT) y[d] = rnnt_act(w.act, (y[d] - mean) * rstd * w.gamma[d] + w.beta[d]);
+  __syncthreads();
+  matvec(w.wp, E, w.J, y, w.bp, pj, red, tid);
+}
+
+// SL: a stateless handle.  The carried state is the id window instead of h / c; the joint block, the argmax and the
+// commit logic are the same code.
+template <bool SL>
 __global__ __launch_bounds__(RNNT_NT) void rnnt_greedy_kernel(RnntDev w, const float* __restrict__ enc_proj,
                                                               const int32_t* __restrict__ row_start,
                                                               const int32_t* __restrict__ row_len, int n_steps,
@@ -127,16 +190,29 @@ __global__ __launch_bounds__(RNNT_NT) void rnnt_greedy_kernel(RnntDev w, const f
   float* gates = xin + (max(w.E, H) + H);   // [4H]
   float* pvec = gates + 4 * H;           // [P]
   float* pj = pvec + w.P;                // [J]
+  // ... of a stateless handle: the window's rows, the mixed vector, the predictor output, reductions, the window
+  float* rows = lds;                     // [Kc][E]
+  float* sx = rows + w.Kc * w.E;         // [E]
+  float* sy = sx + w.E;                  // [E]
+  float* sc = sy + w.E;                  // [32]
+  int* win = reinterpret_cast<int*>(sc + 32);   // [16]
+  if constexpr (SL) pj = sc + 48;
   float* z = pj + J;                     // [RF][J] joint inputs of the block
   float* red = z + RNNT_RF * J;          // [4 * NT] split-K partials (ks * M <= 4 * NT)
   float* wbest = red + 4 * RNNT_NT;      // [8 waves][RF] best value
   int* wbidx = reinterpret_cast<int*>(wbest + 8 * RNNT_RF);  // [8][RF] its id
   int* ctl = wbidx + 8 * RNNT_RF;        // [RF] decisions of the block
 
-  for (int e = tid; e < nl * H; e += RNNT_NT) { h[e] = 0.f; c[e] = 0.f; }
-  __syncthreads();
   int tok = w.blank;
-  predictor(w, tok, h, c, hn, cn, xin, gates, pvec, pj, red, tid);
+  if constexpr (SL) {
+    if (tid < w.Kc) win[tid] = tid == w.Kc - 1 ? tok : -1;
+    __syncthreads();
+    sl_predictor(w, win, rows, sx, sy, pj, red, sc, tid);
+  } else {
+    for (int e = tid; e < nl * H; e += RNNT_NT) { h[e] = 0.f; c[e] = 0.f; }
+    __syncthreads();
+    predictor(w, tok, h, c, hn, cn, xin, gates, pvec, pj, red, tid);
+  }
 
   int t = 0, step = 0;
   while (t < T) {
@@ -216,11 +292,20 @@ __global__ __launch_bounds__(RNNT_NT) void rnnt_greedy_kernel(RnntDev w, const f
     const int k = ctl[f];
     if (tid == 0) out[(size_t)(r0 + t) * n_steps + step] = k;
     ++step;
-    // commit the emission: the predictor's new state becomes the state, k the next input
-    for (int e = tid; e < nl * H; e += RNNT_NT) { h[e] = hn[e]; c[e] = cn[e]; }
-    __syncthreads();
     tok = (unsigned)k < (unsigned)w.V ? k : w.blank;   // NaN logits leave no valid id: never index past embed
-    predictor(w, tok, h, c, hn, cn, xin, gates, pvec, pj, red, tid);
+    if constexpr (SL) {
+      // commit the emission: the id window shifts by k
+      const int nv = tid + 1 < w.Kc ? win[tid + 1] : tok;
+      __syncthreads();
+      if (tid < w.Kc) win[tid] = nv;
+      __syncthreads();
+      sl_predictor(w, win, rows, sx, sy, pj, red, sc, tid);
+    } else {
+      // commit the emission: the predictor's new state becomes the state, k the next input
+      for (int e = tid; e < nl * H; e += RNNT_NT) { h[e] = hn[e]; c[e] = cn[e]; }
+      __syncthreads();
+      predictor(w, tok, h, c, hn, cn, xin, gates, pvec, pj, red, tid);
+    }
     if (step == n_steps) { ++t; step = 0; }
   }
 }
@@ -603,6 +688,10 @@ __host__ __device__ size_t rnnt_grid_lds_bytes(const RnntDev& w) {
 
 size_t rnnt_lds_bytes(const RnntDev& w) {
   const size_t H = w.H, J = w.J, P = w.P;
+  if (w.kind != CFM_RNNT_PRED_RNN) {   // the stateless carve: rows, x, y, reductions + window, pj, then as below
+    const size_t f = (size_t)w.Kc * w.E + 2 * (size_t)w.E + 48 + J + RNNT_RF * J + 4 * RNNT_NT + 8 * RNNT_RF;
+    return f * 4 + 8 * RNNT_RF * 4 + RNNT_RF * 4;
+  }
   size_t f = 4 * w.nl * H + (std::max<size_t>(w.E, H) + H) + 4 * H + P + J + RNNT_RF * J + 4 * RNNT_NT +
              8 * RNNT_RF;
   return f * 4 + 8 * RNNT_RF * 4 + RNNT_RF * 4;
@@ -628,7 +717,7 @@ struct Img {
 // block-major slices of the grid path for h->grid_blocks workgroups (the ranges of rg_range)
 int rnnt_grid_build(cfm_rnnt* h) {
   if (h->grid_mem) { (void)hipFree(h->grid_mem); h->grid_mem = nullptr; }
-  const int G = h->grid_blocks;
+  const int G = h->w.kind != CFM_RNNT_PRED_RNN ? 0 : h->grid_blocks;
   h->gw = RnntGrid{};
   h->gw.G = G;
   if (G <= 0) return 0;
@@ -701,13 +790,30 @@ extern "C" {
 
 cfm_status cfm_rnnt_create(const cfm_rnnt_config* cfg, const cfm_tensor_view* weights, int32_t n, int32_t device,
                            cfm_rnnt** out) {
+  return cfm_rnnt_create_ex(cfg, nullptr, weights, n, device, out);
+}
+
+cfm_status cfm_rnnt_create_ex(const cfm_rnnt_config* cfg, const cfm_rnnt_predictor_config* pcfg,
+                              const cfm_tensor_view* weights, int32_t n, int32_t device, cfm_rnnt** out) {
   if (!cfg || !out || (!weights && n > 0)) return set_error(CFM_ERR_VALUE, "null argument");
   *out = nullptr;
-  const int V = cfg->vocab, E = cfg->embed_size, H = cfg->hidden, nl = cfg->num_layers, P = cfg->pred_out,
-            J = cfg->join_dim, Ee = cfg->enc_dim;
-  if (V < 2 || nl < 1 || nl > RNNT_MAXL) return set_error(CFM_ERR_ASSERT, "vocab >= 2 and 1 <= num_layers <= 4");
-  for (int v : {E, H, P, J, Ee})
+  const int kind = pcfg ? pcfg->kind : CFM_RNNT_PRED_RNN;
+  if (kind != CFM_RNNT_PRED_RNN && kind != CFM_RNNT_PRED_EMBEDDING && kind != CFM_RNNT_PRED_CONV)
+    return set_error(CFM_ERR_VALUE, "predictor kind: rnn, embedding or conv");
+  const bool sl = kind != CFM_RNNT_PRED_RNN;
+  const int V = cfg->vocab, E = cfg->embed_size, H = sl ? 0 : cfg->hidden, nl = sl ? 0 : cfg->num_layers,
+            P = cfg->pred_out, J = cfg->join_dim, Ee = cfg->enc_dim;
+  if (V < 2 || (!sl && (nl < 1 || nl > RNNT_MAXL))) return set_error(CFM_ERR_ASSERT, "vocab >= 2 and 1 <= num_layers <= 4");
+  for (int v : {E, sl ? E : H, P, J, Ee})
     if (v <= 0 || v % 4 || v > 1024) return set_error(CFM_ERR_ASSERT, "predictor / joint widths: multiples of 4, <= 1024");
+  if (sl) {
+    if (E != P) return set_error(CFM_ERR_ASSERT, "stateless predictors need embed_size == output_size");
+    if (pcfg->history_size < 0 || pcfg->history_size > 8) return set_error(CFM_ERR_ASSERT, "history_size: 0 .. 8");
+    if (kind == CFM_RNNT_PRED_EMBEDDING && pcfg->n_head < 1) return set_error(CFM_ERR_ASSERT, "n_head >= 1");
+    if (pcfg->activation < CFM_RNNT_ACT_RELU || pcfg->activation > CFM_RNNT_ACT_GELU)
+      return set_error(CFM_ERR_ASSERT, "predictor activation: relu, swish, tanh or gelu");
+    if (!(pcfg->ln_eps > 0.f)) return set_error(CFM_ERR_ASSERT, "layer_norm_epsilon must be > 0");
+  }
   if (Ee % 32) return set_error(CFM_ERR_ASSERT, "enc_output_size must be a multiple of 32");
   if (cfg->blank < 0 || cfg->blank >= V) return set_error(CFM_ERR_VALUE, "blank id out of range");
   std::map<std::string, std::pair<const float*, int64_t>> m;
@@ -726,6 +832,7 @@ cfm_status cfm_rnnt_create(const cfm_rnnt_config* cfg, const cfm_tensor_view* we
   };
   auto h = std::make_unique<cfm_rnnt>();
   h->cfg = *cfg;
+  if (sl) h->cfg.hidden = h->cfg.num_layers = 0;   // ignored for a stateless handle: no later reader sees the caller's
   h->device = device;
   Img img;
   RnntDev& w = h->w;
@@ -733,6 +840,47 @@ cfm_status cfm_rnnt_create(const cfm_rnnt_config* cfg, const cfm_tensor_view* we
   try {
     const float* emb = get("predictor.embed.weight", (int64_t)V * E);
     img.put(std::vector<float>(emb, emb + (size_t)V * E), &w.embed);
+    w.kind = kind;
+    if (sl) {
+      const int Kc = pcfg->history_size + 1;
+      w.Kc = Kc; w.act = pcfg->activation; w.ln_eps = pcfg->ln_eps;
+      std::vector<float> tap((size_t)Kc * E);
+      if (kind == CFM_RNNT_PRED_EMBEDDING) {
+        // the heads of pos_embed only ever appear summed: q_c[d] = sum_head weight[head, d * Kc + c], once here
+        const int nh = pcfg->n_head;
+        const float* pos = get("predictor.pos_embed.weight", (int64_t)nh * E * Kc);
+        for (int c = 0; c < Kc; ++c)
+          for (int d = 0; d < E; ++d) {
+            double a = 0.0;
+            for (int q = 0; q < nh; ++q) a += pos[((size_t)q * E + d) * Kc + c];
+            tap[(size_t)c * E + d] = (float)a;
+          }
+        w.mix_div = (float)(nh * Kc);
+        h->host_wf = transpose(get("predictor.ffn.weight", (int64_t)E * E), E, E, E);
+        img.put(h->host_wf, &w.wf);
+        const float* bf = get("predictor.ffn.bias", E);
+        img.put(std::vector<float>(bf, bf + E), &w.bf);
+      } else {
+        const float* cw = get("predictor.conv.weight", (int64_t)E * Kc);
+        for (int c = 0; c < Kc; ++c)
+          for (int d = 0; d < E; ++d) tap[(size_t)c * E + d] = cw[(size_t)d * Kc + c];
+        if (pcfg->conv_bias) {
+          const float* cb = get("predictor.conv.bias", E);
+          img.put(std::vector<float>(cb, cb + E), &w.cbias);
+        }
+      }
+      img.put(tap, &w.tap);
+      const float* ga = get("predictor.norm.weight", E);
+      const float* be2 = get("predictor.norm.bias", E);
+      img.put(std::vector<float>(ga, ga + E), &w.gamma);
+      img.put(std::vector<float>(be2, be2 + E), &w.beta);
+      // a non-linearity stands between the predictor and the joint's pred_ffn: it stays a separate [J, E] product
+      const float* wpjm = get("joint.pred_ffn.weight", (int64_t)J * E);
+      const float* bpj = get("joint.pred_ffn.bias", J);
+      h->host_wp = transpose(wpjm, J, E, J);   // [E][J]
+      img.put(h->host_wp, &w.wp);
+      img.put(std::vector<float>(bpj, bpj + J), &w.bp);
+    }
     for (int l = 0; l < nl; ++l) {
       const int in = l == 0 ? E : H;
       const std::string s = std::to_string(l);
@@ -749,34 +897,36 @@ cfm_status cfm_rnnt_create(const cfm_rnnt_config* cfg, const cfm_tensor_view* we
       h->host_wg.push_back(std::move(a));
       h->host_bg.push_back(std::move(bias));
     }
-    // projection (predictor.py:204) and the joint's pred_ffn (joint.py:86) are consecutive Linear
-    // layers with nothing between them: composed once here (f64 products, f32 result) into one
-    // [J, H] matrix, so an emission's predictor runs one matrix-vector product fewer (and the
-    // multi-CU search one grid barrier fewer)
-    const float* wpm = get("predictor.projection.weight", (int64_t)P * H);
-    const float* bp = get("predictor.projection.bias", P);
-    const float* wpjm = get("joint.pred_ffn.weight", (int64_t)J * P);
-    const float* bpj = get("joint.pred_ffn.bias", J);
-    std::vector<float> wc((size_t)J * H), bc(J);
-    {
-      std::vector<double> row(H);
-      for (int j = 0; j < J; ++j) {
-        std::fill(row.begin(), row.end(), 0.0);
-        double b = bpj[j];
-        for (int q = 0; q < P; ++q) {
-          const double a = wpjm[(size_t)j * P + q];
-          const float* src = wpm + (size_t)q * H;
-          for (int k = 0; k < H; ++k) row[k] += a * src[k];
-          b += a * bp[q];
+    if (!sl) {
+      // projection (predictor.py:204) and the joint's pred_ffn (joint.py:86) are consecutive Linear
+      // layers with nothing between them: composed once here (f64 products, f32 result) into one
+      // [J, H] matrix, so an emission's predictor runs one matrix-vector product fewer (and the
+      // multi-CU search one grid barrier fewer)
+      const float* wpm = get("predictor.projection.weight", (int64_t)P * H);
+      const float* bp = get("predictor.projection.bias", P);
+      const float* wpjm = get("joint.pred_ffn.weight", (int64_t)J * P);
+      const float* bpj = get("joint.pred_ffn.bias", J);
+      std::vector<float> wc((size_t)J * H), bc(J);
+      {
+        std::vector<double> row(H);
+        for (int j = 0; j < J; ++j) {
+          std::fill(row.begin(), row.end(), 0.0);
+          double b = bpj[j];
+          for (int q = 0; q < P; ++q) {
+            const double a = wpjm[(size_t)j * P + q];
+            const float* src = wpm + (size_t)q * H;
+            for (int k = 0; k < H; ++k) row[k] += a * src[k];
+            b += a * bp[q];
+          }
+          for (int k = 0; k < H; ++k) wc[(size_t)j * H + k] = (float)row[k];
+          bc[j] = (float)b;
         }
-        for (int k = 0; k < H; ++k) wc[(size_t)j * H + k] = (float)row[k];
-        bc[j] = (float)b;
       }
+      w.P = J;   // the composed product's width: pvec is the pred_ffn output
+      h->host_wp = transpose(wc.data(), J, H, J);   // [H][J]
+      img.put(h->host_wp, &w.wp);
+      img.put(bc, &w.bp);
     }
-    w.P = J;   // the composed product's width: pvec is the pred_ffn output
-    h->host_wp = transpose(wc.data(), J, H, J);   // [H][J]
-    img.put(h->host_wp, &w.wp);
-    img.put(bc, &w.bp);
     h->host_wo = transpose(get("joint.ffn_out.weight", (int64_t)V * J), V, J, w.Vp);
     img.put(h->host_wo, &w.wo);
     const float* bo = get("joint.ffn_out.bias", V);
@@ -814,6 +964,7 @@ cfm_status cfm_rnnt_set_option(cfm_rnnt* h, const char* key, int64_t value) {
   if (!h || !key) return set_error(CFM_ERR_VALUE, "null argument");
   if (std::string(key) == "grid_blocks") {
     if (value < 0 || value > 256) return set_error(CFM_ERR_VALUE, "grid_blocks: 0 (off) .. 256");
+    if (h->w.kind != CFM_RNNT_PRED_RNN) return CFM_OK;   // accepted, no effect: a stateless handle has no grid path
     h->grid_blocks = (int)value;
     if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       return set_error(CFM_ERR_RUNTIME, "rnnt: device sync");
@@ -842,6 +993,7 @@ cfm_status cfm_rnnt_set_option(cfm_rnnt* h, const char* key, int64_t value) {
 
 int32_t cfm_rnnt_grid_blocks(const cfm_rnnt* h, int32_t B) {
   if (!h || B <= 0 || h->grid_blocks <= 0 || B > RG_MAXB || (int64_t)B * h->grid_blocks > h->n_cu) return 0;
+  if (h->w.kind != CFM_RNNT_PRED_RNN) return 0;   // the multi-CU search is built for the LSTM predictor only
   const int G = h->grid_blocks;
   // the joint's per-workgroup candidates reuse the z block: <= 64 column groups per workgroup, J >= 128
   if ((h->w.Vp / 4 + G - 1) / G > 64 || h->w.J < 128) return 0;
@@ -930,11 +1082,16 @@ cfm_status cfm_rnnt_greedy_ex(const cfm_rnnt* h, const float* enc, int32_t rows,
     }
   }
   const size_t lds = rnnt_lds_bytes(h->w);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)rnnt_greedy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+  const bool sl = h->w.kind != CFM_RNNT_PRED_RNN;
+  const void* kern = sl ? (const void*)rnnt_greedy_kernel<true> : (const void*)rnnt_greedy_kernel<false>;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return set_error(CFM_ERR_RUNTIME, "rnnt: dynamic LDS attribute");
-  hipLaunchKernelGGL(rnnt_greedy_kernel, dim3(B), dim3(RNNT_NT), lds, st, h->w, proj, row_start, row_len, n_steps,
-                     out);
+  if (sl)
+    hipLaunchKernelGGL(rnnt_greedy_kernel<true>, dim3(B), dim3(RNNT_NT), lds, st, h->w, proj, row_start, row_len,
+                       n_steps, out);
+  else
+    hipLaunchKernelGGL(rnnt_greedy_kernel<false>, dim3(B), dim3(RNNT_NT), lds, st, h->w, proj, row_start, row_len,
+                       n_steps, out);
   const hipError_t le = hipGetLastError();
   if (le != hipSuccess) return set_error(CFM_ERR_RUNTIME, std::string("rnnt_greedy_kernel: ") + hipGetErrorString(le));
   return CFM_OK;

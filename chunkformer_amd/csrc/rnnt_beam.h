@@ -24,6 +24,11 @@ struct RbWS {
   float *xh[RNNT_MAXL][2], *c[RNNT_MAXL][2], *hn[RNNT_MAXL], *cn[RNNT_MAXL];
   float *gates, *pj, *z, *logits;
   size_t act_off, act_bytes;   // the activations: zeroed before a search (the initial LSTM state)
+  // a stateless handle: the K_c - 1 ids before each slot's last token (-1 = before the sos), two buffers; the last
+  // token as the context kernel saw it (the prune kernel overwrites tok); the mixed vector and the predictor output
+  int32_t *hist[2], *ptok;
+  size_t hist_off, hist_bytes;   // set to 0xff (-1) before a search
+  float *sx, *sy;
 };
 
 // the GEMM operands in [N][K] layout, once per handle (0 = ok)
@@ -37,6 +42,11 @@ int rb_gemm(const float* A, int lda, const float* W, const float* bias, int M, i
 // embedding, LSTM layers, composed projection + pred_ffn for the live rows: state (h in xh[l][cur]'s h part, c in
 // c[l][cur]) -> hn / cn (the state after this token) and pj
 cfm_status rb_predictor(const cfm_rnnt* h, const RbWS& s, const RbLive& lv, int R, int cur, hipStream_t st);
+// The stateless predictors for the live rows: row r's window is hist[r * hist_ld .. + Kc - 1) then last[r * last_ld]
+// (ids, -1 = a zero vector) -> x (mix), y (predictor output) [R, E], pj = pred_ffn(y) [R, J]; ptok (or null) receives
+// the last id of every live row
+cfm_status sl_predictor(const cfm_rnnt* h, const RbLive& lv, const int32_t* hist, int hist_ld, const int32_t* last,
+                        int last_ld, int R, int32_t* ptok, float* x, float* y, float* pj, hipStream_t st);
 // ustart / ulen / the start beam of every utterance (a bad row range sets the error word and counts as no rows)
 int rb_init(const int32_t* row_start, const int32_t* row_len, int B, int K, int rows, int max_len, int blank,
             const RbWS& s, hipStream_t st);

@@ -16,6 +16,10 @@
 //   rb_gather_kernel       the survivors' LSTM state by parent slot (the new state for an appended token, the old one
 //                          for an unchanged hypothesis) into the other of two buffers
 //
+// A stateless handle (embedding / conv predictor) replaces the embed .. projection launches by sl_ctx_kernel (the slot's
+// Kc context rows mixed into x), the ffn gemm<float> (embedding only), sl_norm_act_kernel and the pred_ffn gemm<float>,
+// and rb_gather_kernel by sl_gather_kernel, which moves Kc - 1 int32 ids per slot (nothing with history_size 0).
+//
 // The predictor is evaluated for every live hypothesis at every frame, as the reference does; an unchanged
 // hypothesis keeps its old state, so its next evaluation repeats the same values.
 //
@@ -120,6 +124,93 @@ __global__ __launch_bounds__(128) void rb_joint_in_kernel(RbLive lv, const float
   if (!rb_live(lv, r, &src)) return;
   for (int j = threadIdx.x; j < J; j += 128)
     z[(size_t)r * J + j] = tanhf(enc_proj[(size_t)src * J + j] + pj[(size_t)r * J + j]);
+}
+
+// ----------------------------------------------------------------------------- the stateless predictors
+// One workgroup per live row: the row's Kc context rows (id -1: a zero vector) and their mix into x.  embedding:
+// x = sum_c (c_c . q_c) c_c / (n_head Kc), each dot product by one wave; conv: x[d] = sum_c tap[c][d] c_c[d] (+ bias).
+__global__ __launch_bounds__(256) void sl_ctx_kernel(RbLive lv, RnntDev w, const int32_t* __restrict__ hist, int hist_ld,
+                                                     const int32_t* __restrict__ last, int last_ld,
+                                                     int32_t* __restrict__ ptok, float* __restrict__ x) {
+  extern __shared__ float sl_rows[];   // [Kc][E], then [16] dot products
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int src;
+  if (!rb_live(lv, r, &src)) return;
+  const int E = w.E, Kc = w.Kc;
+  float* dots = sl_rows + Kc * E;
+  const int lt = last[(size_t)r * last_ld];
+  if (ptok && tid == 0) ptok[r] = lt;
+  for (int e = tid; e < Kc * E; e += 256) {
+    const int c = e / E, d = e - c * E;
+    const int id = c == Kc - 1 ? lt : hist[(size_t)r * hist_ld + c];
+    sl_rows[e] = id >= 0 ? w.embed[(size_t)min(id, w.V - 1) * E + d] : 0.f;
+  }
+  __syncthreads();
+  if (w.kind == CFM_RNNT_PRED_EMBEDDING) {
+    for (int c = wid; c < Kc; c += 4) {
+      float s = 0.f;
+      for (int d = lane; d < E; d += 64) s = fmaf(sl_rows[c * E + d], w.tap[c * E + d], s);
+      s = wave_sum(s);
+      if (lane == 0) dots[c] = s;
+    }
+    __syncthreads();
+    for (int d = tid; d < E; d += 256) {
+      float a = 0.f;
+      for (int c = 0; c < Kc; ++c) a = fmaf(dots[c], sl_rows[c * E + d], a);
+      x[(size_t)r * E + d] = a / w.mix_div;
+    }
+  } else {
+    for (int d = tid; d < E; d += 256) {
+      float a = 0.f;
+      for (int c = 0; c < Kc; ++c) a = fmaf(w.tap[c * E + d], sl_rows[c * E + d], a);
+      x[(size_t)r * E + d] = w.cbias ? a + w.cbias[d] : a;
+    }
+  }
+}
+
+// y = act(LayerNorm(v)) per live row (two passes: the mean, then the variance about it), one workgroup per row.
+// v may be y (the embedding kind runs it in place on the ffn output): element d is read and written by one thread only.
+__global__ __launch_bounds__(256) void sl_norm_act_kernel(RbLive lv, RnntDev w, const float* v, float* y) {
+  __shared__ float s_red[8];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int src;
+  if (!rb_live(lv, r, &src)) return;
+  const int E = w.E;
+  const float* in = v + (size_t)r * E;
+  float s = 0.f;
+  for (int d = tid; d < E; d += 256) s += in[d];
+  s = wave_sum(s);
+  if (lane == 0) s_red[wid] = s;
+  __syncthreads();
+  const float mean = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (float)E;
+  float q = 0.f;
+  for (int d = tid; d < E; d += 256) { const float dd = in[d] - mean; q = fmaf(dd, dd, q); }
+  q = wave_sum(q);
+  if (lane == 0) s_red[4 + wid] = q;
+  __syncthreads();
+  const float rstd = 1.f / sqrtf(((s_red[4] + s_red[5]) + (s_red[6] + s_red[7])) / (float)E + w.ln_eps);
+  for (int d = tid; d < E; d += 256)
+    y[(size_t)r * E + d] = rnnt_act(w.act, (in[d] - mean) * rstd * w.gamma[d] + w.beta[d]);
+}
+
+// the survivors' id history: slot k < n[b] takes its parent's window shifted by the parent's last token (a token was
+// appended) or the parent's history as it was.  hl = Kc - 1 >= 1 ids per slot.
+__global__ __launch_bounds__(64) void sl_gather_kernel(RbLive lv, const int32_t* __restrict__ par,
+                                                       const int32_t* __restrict__ chg, int R, int hl,
+                                                       const int32_t* __restrict__ h_old,
+                                                       const int32_t* __restrict__ ptok, int32_t* __restrict__ h_out) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  int src;
+  if (r >= R || !rb_live(lv, r, &src)) return;
+  const int b = r / lv.K;
+  const int rp = b * lv.K + min(max(par[r], 0), lv.K - 1);
+  const bool ch = chg[r] != 0;
+  for (int c = 0; c < hl; ++c) {
+    int v;
+    if (!ch) v = h_old[(size_t)rp * hl + c];
+    else v = c + 1 < hl ? h_old[(size_t)rp * hl + c + 1] : ptok[rp];
+    h_out[(size_t)r * hl + c] = v;
+  }
 }
 
 // ----------------------------------------------------------------------------- log-softmax + CTC fusion + top K
@@ -380,7 +471,9 @@ int rb_weights(cfm_rnnt* h) {
     const int in = l == 0 ? w.E : w.H;
     put_t(h->host_wg[l], in + w.H, 4 * w.H, 4 * w.H, &h->bw_g[l]);
   }
-  put_t(h->host_wp, w.H, w.J, w.J, &h->bw_p);
+  const bool sl = w.kind != CFM_RNNT_PRED_RNN;
+  put_t(h->host_wp, sl ? w.E : w.H, w.J, w.J, &h->bw_p);   // (a stateless handle: pred_ffn alone, [J][E])
+  if (w.kind == CFM_RNNT_PRED_EMBEDDING) put_t(h->host_wf, w.E, w.E, w.E, &h->bw_f);
   put_t(h->host_wo, w.J, w.Vp, w.V, &h->bw_o);
   void* mem = nullptr;
   if (hipMalloc(&mem, img.size() * 4) != hipSuccess) return 1;
@@ -426,6 +519,18 @@ RbWS rb_carve(const cfm_rnnt* h, void* base, int rows, int B, int K, size_t* tot
   s.gates = c.take<float>(R * 4 * w.H);
   s.pj = c.take<float>(R * w.J);
   s.z = c.take<float>(R * w.J);
+  s.hist[0] = s.hist[1] = s.ptok = nullptr;
+  s.sx = s.sy = nullptr;
+  s.hist_off = s.hist_bytes = 0;
+  if (w.kind != CFM_RNNT_PRED_RNN) {   // the state of a slot is Kc - 1 ids (none with history_size 0)
+    s.sx = c.take<float>(R * w.E);
+    s.sy = c.take<float>(R * w.E);
+    s.ptok = c.take<int32_t>(R);
+    s.hist_off = c.off;
+    s.hist[0] = c.take<int32_t>(std::max<size_t>(R * (w.Kc - 1), 1));
+    s.hist[1] = c.take<int32_t>(std::max<size_t>(R * (w.Kc - 1), 1));
+    s.hist_bytes = c.off - s.hist_off;
+  }
   s.act_bytes = c.off - s.act_off;
   s.logits = c.take<float>(R * w.V);
   if (total) *total = c.off;
@@ -462,6 +567,23 @@ cfm_status rb_predictor(const cfm_rnnt* h, const RbWS& s, const RbLive& lv, int 
     KCHK((int)hipGetLastError());
   }
   KCHK(rb_gemm(s.hn[w.nl - 1], w.H, h->bw_p, w.bp, R, w.J, w.H, s.pj, w.J, st));
+  return CFM_OK;
+}
+
+cfm_status sl_predictor(const cfm_rnnt* h, const RbLive& lv, const int32_t* hist, int hist_ld, const int32_t* last,
+                        int last_ld, int R, int32_t* ptok, float* x, float* y, float* pj, hipStream_t st) {
+  const RnntDev& w = h->w;
+  const size_t lds = ((size_t)w.Kc * w.E + 16) * sizeof(float);   // <= 9 * 1024 + 16 floats
+  hipLaunchKernelGGL(sl_ctx_kernel, dim3(R), dim3(256), lds, st, lv, w, hist, hist_ld, last, last_ld, ptok, x);
+  KCHK((int)hipGetLastError());
+  const float* v = x;
+  if (w.kind == CFM_RNNT_PRED_EMBEDDING) {
+    KCHK(rb_gemm(x, w.E, h->bw_f, w.bf, R, w.E, w.E, y, w.E, st));
+    v = y;
+  }
+  hipLaunchKernelGGL(sl_norm_act_kernel, dim3(R), dim3(256), 0, st, lv, w, v, y);
+  KCHK((int)hipGetLastError());
+  KCHK(rb_gemm(y, w.E, h->bw_p, w.bp, R, w.J, w.E, pj, w.J, st));
   return CFM_OK;
 }
 
@@ -545,7 +667,8 @@ cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc, int32_t rows, con
   const int K = beam, R = B * K;
   const RbWS s = rb_carve(h, ws, rows, B, K, nullptr);
   if (hipMemsetAsync(s.err, 0, s.zero_bytes, st) != hipSuccess ||
-      hipMemsetAsync((char*)ws + s.act_off, 0, s.act_bytes, st) != hipSuccess)
+      hipMemsetAsync((char*)ws + s.act_off, 0, s.act_bytes, st) != hipSuccess ||
+      (s.hist_bytes && hipMemsetAsync((char*)ws + s.hist_off, 0xff, s.hist_bytes, st) != hipSuccess))   // ids -1
     return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
   if (trace && rows > 0) {
     const size_t rk = (size_t)rows * K;
@@ -572,7 +695,13 @@ cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc, int32_t rows, con
   for (int t = 0; t < max_len; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     const RbLive lv{s.ustart, s.ulen, s.n, K, t};
-    if (const cfm_status e = rb_predictor(h, s, lv, R, cur, st)) return e;
+    const bool sl = w.kind != CFM_RNNT_PRED_RNN;
+    if (sl) {
+      if (const cfm_status e = sl_predictor(h, lv, s.hist[cur], w.Kc - 1, s.tok, 1, R, s.ptok, s.sx, s.sy, s.pj, st))
+        return e;
+    } else if (const cfm_status e = rb_predictor(h, s, lv, R, cur, st)) {
+      return e;
+    }
     hipLaunchKernelGGL(rb_joint_in_kernel, dim3(R), dim3(128), 0, st, lv, s.enc_proj, s.pj, w.J, s.z);
     KCHK((int)hipGetLastError());
     KCHK(rb_gemm(s.z, w.J, h->bw_o, w.bo, R, w.V, w.J, s.logits, w.V, st));
@@ -583,6 +712,11 @@ cfm_status cfm_rnnt_beam_search(cfm_rnnt* h, const float* enc, int32_t rows, con
     hipLaunchKernelGGL(rb_prune_kernel, dim3(B), dim3(256), 0, st, a, t, s.tv, s.ti);
     KCHK((int)hipGetLastError());
     // the new beam's state into the other buffers (n[b] is the new count: slots the prune kernel wrote)
+    if (sl && w.Kc > 1) {
+      hipLaunchKernelGGL(sl_gather_kernel, dim3((R + 63) / 64), dim3(64), 0, st, lv, s.par, s.chg, R, w.Kc - 1,
+                         s.hist[cur], s.ptok, s.hist[nxt]);
+      KCHK((int)hipGetLastError());
+    }
     for (int l = 0; l < w.nl; ++l) {
       const int in = l == 0 ? w.E : w.H;
       hipLaunchKernelGGL(rb_gather_kernel, dim3(R), dim3(128), 0, st, lv, s.par, s.chg, w.H, s.xh[l][cur] + in,
@@ -658,8 +792,32 @@ cfm_status cfm_op_rnnt_beam_prune(const float* topk_vals, const int32_t* topk_id
   return CFM_OK;
 }
 
+size_t cfm_op_rnnt_predictor_step_workspace_bytes(const cfm_rnnt* h, int32_t R) {
+  if (!h || R < 1 || R > (1 << 20) || h->w.kind == CFM_RNNT_PRED_RNN) return 0;
+  return (size_t)R * h->w.E * sizeof(float) + 256;
+}
+
+cfm_status cfm_op_rnnt_predictor_step(cfm_rnnt* h, const int32_t* windows, int32_t R, float* y_out, float* pred_out,
+                                      void* ws, size_t wsb, cfm_stream stream) {
+  if (!h) return set_error(CFM_ERR_VALUE, "null handle");
+  if (h->w.kind == CFM_RNNT_PRED_RNN) return set_error(CFM_ERR_VALUE, "predictor step: not a stateless handle");
+  if (R < 1 || R > (1 << 20)) return set_error(CFM_ERR_VALUE, "predictor step: bad R");
+  if (!windows || !y_out || !pred_out || !ws) return set_error(CFM_ERR_VALUE, "null argument");
+  if (!rb_widths_ok(h))
+    return set_error(CFM_ERR_ASSERT, "rnnt beam search: embed_size, hidden_size and join_dim must be multiples of 32");
+  if (wsb < cfm_op_rnnt_predictor_step_workspace_bytes(h, R)) return set_error(CFM_ERR_VALUE, "predictor step workspace too small");
+  if ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(y_out) | reinterpret_cast<uintptr_t>(pred_out)) & 15)
+    return set_error(CFM_ERR_VALUE, "workspace / outputs must be 16-byte aligned");
+  if (hipSetDevice(h->device) != hipSuccess) return set_error(CFM_ERR_RUNTIME, "hipSetDevice");
+  if (rb_weights(h)) return set_error(CFM_ERR_RUNTIME, "rnnt beam search: weights upload");
+  const RbLive lv{nullptr, nullptr, nullptr, 1, 0};
+  const int Kc = h->w.Kc;
+  return sl_predictor(h, lv, windows, Kc, windows + Kc - 1, Kc, R, nullptr, (float*)ws, y_out, pred_out,
+                      (hipStream_t)stream);
+}
+
 size_t cfm_op_rnnt_lstm_step_workspace_bytes(const cfm_rnnt* h, int32_t R) {
-  if (!h || R < 1 || R > (1 << 20)) return 0;
+  if (!h || R < 1 || R > (1 << 20) || h->w.kind != CFM_RNNT_PRED_RNN) return 0;
   size_t t = 0;
   rb_carve(h, nullptr, 0, R, 1, &t);
   return t + 256;
@@ -668,6 +826,7 @@ size_t cfm_op_rnnt_lstm_step_workspace_bytes(const cfm_rnnt* h, int32_t R) {
 cfm_status cfm_op_rnnt_lstm_step(cfm_rnnt* h, const int32_t* tokens, const float* h_in, const float* c_in, int32_t R,
                                  float* h_out, float* c_out, float* pred_out, void* ws, size_t wsb, cfm_stream stream) {
   if (!h) return set_error(CFM_ERR_VALUE, "null handle");
+  if (h->w.kind != CFM_RNNT_PRED_RNN) return set_error(CFM_ERR_VALUE, "lstm step: not an LSTM handle");
   if (R < 1 || R > (1 << 20)) return set_error(CFM_ERR_VALUE, "lstm step: bad R");
   if (!tokens || !h_in || !c_in || !h_out || !c_out || !pred_out || !ws) return set_error(CFM_ERR_VALUE, "null argument");
   if (!rb_widths_ok(h))

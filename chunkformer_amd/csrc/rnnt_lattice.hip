@@ -11,6 +11,8 @@
 //   per step s <= max U  rl_step_kernel (state s's consumed token per hypothesis), the beam search's predictor step
 //                        (rb_predictor: embedding, LSTM layers, composed projection + pred_ffn), rl_advance_kernel
 //                        (pj -> pred_proj[first_state + s], the new LSTM state becomes the state)
+//   (a stateless handle)  instead of those steps: rl_window_kernel (the id window of every state) and one pass of the
+//                        beam search's stateless predictor (sl_predictor) over all n_states states -> pred_proj
 //   rl_joint_kernel      one workgroup per tile of 32 or 64 consecutive nodes (tiles straddle hypotheses and end inside
 //                        a lattice): z = tanh(e_t + p_u) is formed once into LDS and stays there for the whole sweep
 //                        over V; ffn_out streams through LDS in tiles of 128 vocabulary rows x 32 (bf16: 64) columns of K (the
@@ -316,6 +318,23 @@ __global__ __launch_bounds__(128) void rl_advance_kernel(const RlState a, const 
     }
 }
 
+// A stateless handle: the id window of every state of every hypothesis, win [n_states][Kc] (oldest first, -1 = a zero
+// vector).  State s of hypothesis i reads tokens[max(first_state, s - Kc + 1) .. s]: never the previous hypothesis'
+// tokens in the packed array.  A state that no valid hypothesis owns keeps the all -1 window the caller set.
+__global__ __launch_bounds__(64) void rl_window_kernel(const int32_t* __restrict__ desc, const int32_t* __restrict__ tokens,
+                                                       const int32_t* __restrict__ hyp_t, int n_states, int max_u1, int Kc,
+                                                       int V, int32_t* __restrict__ win) {
+  const int i = blockIdx.x;
+  if (hyp_t[i] <= 0) return;   // (rl_check_kernel: the descriptor is outside its arrays)
+  const int st0 = desc[4 * i + 1], U1 = min(desc[4 * i + 2], max_u1);
+  for (int e = threadIdx.x; e < U1 * Kc; e += 64) {
+    const int u = e / Kc, c = e - u * Kc;
+    const int p = u - (Kc - 1) + c;   // the position in the hypothesis' own states
+    if (st0 + u >= n_states) continue;
+    win[(size_t)(st0 + u) * Kc + c] = p >= 0 ? min(max(tokens[st0 + p], 0), V - 1) : -1;
+  }
+}
+
 // ----------------------------------------------------------------------------- the recursion
 // The two diagonals are addressed as (which, u): in LDS through the shared array itself, in the workspace through the
 // global pointer -- never through one pointer that may be either (a generic pointer to LDS offset 0 minus one element
@@ -456,6 +475,8 @@ struct RlWS {
   int32_t *hyp_t, *hyp_u1;
   float *pred_proj, *b, *k;
   double* spill;
+  int32_t* win;       // a stateless handle: [n_states][Kc] id windows, the mixed vectors and the predictor outputs
+  float *sx, *sy;     // [n_states][E]
 };
 
 bool rl_geom_ok(const cfm_rnnt* h, int rows, int n_hyp, int n_states, int max_u1, int64_t total) {
@@ -476,6 +497,13 @@ RlWS rl_carve(const cfm_rnnt* h, void* base, int rows, int n_hyp, int n_states, 
   s.b = c.take<float>((size_t)total);
   s.k = c.take<float>((size_t)total);
   s.spill = c.take<double>(max_u1 > RL_ALPHA_LDS ? (size_t)n_hyp * 2 * max_u1 : 1);
+  s.win = nullptr;
+  s.sx = s.sy = nullptr;
+  if (h->w.kind != CFM_RNNT_PRED_RNN) {
+    s.win = c.take<int32_t>((size_t)n_states * h->w.Kc);
+    s.sx = c.take<float>((size_t)n_states * h->w.E);
+    s.sy = c.take<float>((size_t)n_states * h->w.E);
+  }
   if (bytes) *bytes = c.off;
   return s;
 }
@@ -540,7 +568,18 @@ cfm_status cfm_rnnt_td_score(cfm_rnnt* h, const float* enc, int32_t rows, const 
     ps.c[l] = r.c[l][0]; ps.hn[l] = r.hn[l]; ps.cn[l] = r.cn[l];
   }
   const RbLive lv{nullptr, nullptr, nullptr, 1, 0};
-  for (int step = 0; step < max_u1; ++step) {
+  if (w.kind != CFM_RNNT_PRED_RNN) {
+    // the predictor is a function of the last Kc ids: one pass over all n_states states, no sequential steps
+    if (hipMemsetAsync(s.win, 0xff, (size_t)n_states * w.Kc * 4, st) != hipSuccess)
+      return set_error(CFM_ERR_RUNTIME, "hipMemsetAsync");
+    hipLaunchKernelGGL(rl_window_kernel, dim3(n_hyp), dim3(64), 0, st, desc, tokens, s.hyp_t, n_states, max_u1, w.Kc, w.V,
+                       s.win);
+    KCHK((int)hipGetLastError());
+    if (const cfm_status e = sl_predictor(h, lv, s.win, w.Kc, s.win + w.Kc - 1, w.Kc, n_states, nullptr, s.sx, s.sy,
+                                          s.pred_proj, st))
+      return e;
+  }
+  for (int step = 0; w.kind == CFM_RNNT_PRED_RNN && step < max_u1; ++step) {
     hipLaunchKernelGGL(rl_step_kernel, dim3((n_hyp + 63) / 64), dim3(64), 0, st, desc, tokens, n_hyp, n_states, step,
                        r.tok);
     KCHK((int)hipGetLastError());

@@ -9,7 +9,9 @@ Supported predictor / joint: the reference's shipped recipe
 (examples/asr/rnnt/conf/chunkformer-rnnt-large-vie.yaml): `predictor: rnn` with rnn_type lstm
 (transducer/predictor.py:66-208), `joint: transducer_joint` with prejoin_linear, no
 postjoin_linear, joint_mode add, tanh, no HAT (transducer/joint.py:10-111); blank id 0
-(init_model.py:125-128).  Anything else raises AssertionError like the reference's asserts.
+(init_model.py:125-128); and the two stateless predictors of the same factory, `predictor: embedding` and `predictor:
+conv` (predictor.py:210-471), whose state is the last history_size + 1 token ids -- they run on the
+one-workgroup kernel only.  Anything else raises AssertionError like the reference's asserts.
 The predictor and joint run in f32 whatever the encoder's compute dtype.
 """
 from __future__ import annotations
@@ -26,6 +28,11 @@ import torch
 from . import _lib
 
 
+PREDICTORS = ("rnn", "embedding", "conv")
+PREDICTOR_ACTS = ("relu", "swish", "tanh", "gelu")   # CFM_RNNT_ACT_* in this order
+PREDICTOR_DEFAULT_ACT = {"rnn": "", "embedding": "swish", "conv": "relu"}
+
+
 @dataclass
 class RNNTConfig:
     vocab: int = 1024           # output_dim (bpe 1024 in the vie recipe)
@@ -36,41 +43,93 @@ class RNNTConfig:
     pred_out: int = 512         # predictor_conf.output_size (= joint_conf.pred_output_size)
     join_dim: int = 512         # joint_conf.join_dim
     blank: int = 0
+    # the stateless predictors (predictor.py:210-471); hidden / num_layers are unused by them
+    predictor: str = "rnn"      # "rnn" | "embedding" | "conv"
+    history_size: int = 2       # predictor_conf.history_size: the context is the last history_size + 1 tokens
+    n_head: int = 1             # predictor_conf.n_head (embedding)
+    activation: str = ""        # predictor_conf.activation ("" = the kind's default: swish / relu)
+    ln_eps: float = 1e-5        # predictor_conf.layer_norm_epsilon
+    conv_bias: bool = False     # predictor_conf.bias of the conv predictor (the embedding predictor never reads its own)
+    pos_bias: bool = False      # predictor_conf.bias of the embedding predictor: pos_embed.bias exists (and is ignored)
+
+    @property
+    def stateless(self) -> bool:
+        return self.predictor != "rnn"
+
+    @property
+    def context(self) -> int:
+        return self.history_size + 1
+
+    @property
+    def act(self) -> str:
+        return self.activation or PREDICTOR_DEFAULT_ACT[self.predictor]
 
     @classmethod
     def from_conf(cls, conf: dict, vocab: int, enc_dim: int) -> "RNNTConfig":
         """From a reference config.yaml (init_model.py:118-135)."""
-        assert conf.get("predictor", "rnn") == "rnn", "only predictor: rnn is supported"
+        kind = conf.get("predictor", "rnn")
+        assert kind in PREDICTORS, "predictor: rnn, embedding or conv"
         pc = dict(conf.get("predictor_conf") or {})
         jc = dict(conf.get("joint_conf") or {})
         assert conf.get("joint", "transducer_joint") == "transducer_joint"
-        assert pc.get("rnn_type", "lstm") == "lstm", "only rnn_type lstm is supported"
-        assert pc.get("bias", True), "predictor without bias is not supported"
         assert jc.get("prejoin_linear", True) and not jc.get("postjoin_linear", False)
         assert jc.get("joint_mode", "add") == "add" and jc.get("activation", "tanh") == "tanh"
         assert not jc.get("hat_joint", False)
-        c = cls(vocab=int(vocab), enc_dim=int(jc.get("enc_output_size", enc_dim)),
-                embed_size=int(pc["embed_size"]), hidden=int(pc["hidden_size"]), num_layers=int(pc["num_layers"]),
-                pred_out=int(pc["output_size"]), join_dim=int(jc["join_dim"]))
+        if kind == "rnn":
+            assert pc.get("rnn_type", "lstm") == "lstm", "only rnn_type lstm is supported"
+            assert pc.get("bias", True), "predictor without bias is not supported"
+            c = cls(vocab=int(vocab), enc_dim=int(jc.get("enc_output_size", enc_dim)),
+                    embed_size=int(pc["embed_size"]), hidden=int(pc["hidden_size"]), num_layers=int(pc["num_layers"]),
+                    pred_out=int(pc["output_size"]), join_dim=int(jc["join_dim"]))
+        else:
+            act = str(pc.get("activation", PREDICTOR_DEFAULT_ACT[kind]))
+            assert act in PREDICTOR_ACTS, "predictor activation: relu, swish, tanh or gelu"
+            assert int(pc["embed_size"]) == int(pc["output_size"]), "stateless predictors need embed_size == output_size"
+            assert int(pc.get("history_size", 2)) >= 0, "history_size must be >= 0"
+            bias = bool(pc.get("bias", False))
+            c = cls(vocab=int(vocab), enc_dim=int(jc.get("enc_output_size", enc_dim)), embed_size=int(pc["embed_size"]),
+                    hidden=0, num_layers=0, pred_out=int(pc["output_size"]), join_dim=int(jc["join_dim"]),
+                    predictor=kind, history_size=int(pc.get("history_size", 2)),
+                    n_head=int(pc["n_head"]) if kind == "embedding" else 1, activation=act,
+                    ln_eps=float(pc.get("layer_norm_epsilon", 1e-5)), conv_bias=bias and kind == "conv",
+                    pos_bias=bias and kind == "embedding")
         assert int(jc.get("pred_output_size", c.pred_out)) == c.pred_out
         return c
 
     def validate(self) -> None:
-        for v in (self.embed_size, self.hidden, self.pred_out, self.join_dim, self.enc_dim):
+        assert self.predictor in PREDICTORS, "predictor: rnn, embedding or conv"
+        widths = (self.embed_size, self.pred_out, self.join_dim, self.enc_dim)
+        for v in widths + (() if self.stateless else (self.hidden,)):
             assert v % 4 == 0 and 0 < v <= 1024, "predictor / joint widths must be multiples of 4, <= 1024"
-        assert self.num_layers >= 1 and self.vocab > 1
+        assert self.vocab > 1
+        if self.stateless:
+            assert self.embed_size == self.pred_out, "stateless predictors need embed_size == output_size"
+            assert 0 <= self.history_size <= 8, "history_size: 0 .. 8"
+            assert self.n_head >= 1 and self.act in PREDICTOR_ACTS and self.ln_eps > 0
+        else:
+            assert self.num_layers >= 1
 
 
 def schema(c: RNNTConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     """(name, shape) of every predictor / joint tensor, keys as in the reference Transducer."""
-    H = c.hidden
+    H, E = c.hidden, c.embed_size
     out = [("predictor.embed.weight", (c.vocab, c.embed_size))]
-    for l in range(c.num_layers):
-        inp = c.embed_size if l == 0 else H
-        out += [(f"predictor.rnn.weight_ih_l{l}", (4 * H, inp)), (f"predictor.rnn.weight_hh_l{l}", (4 * H, H)),
-                (f"predictor.rnn.bias_ih_l{l}", (4 * H,)), (f"predictor.rnn.bias_hh_l{l}", (4 * H,))]
-    out += [("predictor.projection.weight", (c.pred_out, H)), ("predictor.projection.bias", (c.pred_out,)),
-            ("joint.enc_ffn.weight", (c.join_dim, c.enc_dim)), ("joint.enc_ffn.bias", (c.join_dim,)),
+    if c.predictor == "embedding":
+        out += [("predictor.pos_embed.weight", (c.n_head, E * c.context))]
+        out += [("predictor.pos_embed.bias", (c.n_head,))] if c.pos_bias else []
+        out += [("predictor.ffn.weight", (E, E)), ("predictor.ffn.bias", (E,)),
+                ("predictor.norm.weight", (E,)), ("predictor.norm.bias", (E,))]
+    elif c.predictor == "conv":
+        out += [("predictor.conv.weight", (E, 1, c.context))]
+        out += [("predictor.conv.bias", (E,))] if c.conv_bias else []
+        out += [("predictor.norm.weight", (E,)), ("predictor.norm.bias", (E,))]
+    else:
+        for l in range(c.num_layers):
+            inp = c.embed_size if l == 0 else H
+            out += [(f"predictor.rnn.weight_ih_l{l}", (4 * H, inp)), (f"predictor.rnn.weight_hh_l{l}", (4 * H, H)),
+                    (f"predictor.rnn.bias_ih_l{l}", (4 * H,)), (f"predictor.rnn.bias_hh_l{l}", (4 * H,))]
+        out += [("predictor.projection.weight", (c.pred_out, H)), ("predictor.projection.bias", (c.pred_out,))]
+    out += [("joint.enc_ffn.weight", (c.join_dim, c.enc_dim)), ("joint.enc_ffn.bias", (c.join_dim,)),
             ("joint.pred_ffn.weight", (c.join_dim, c.pred_out)), ("joint.pred_ffn.bias", (c.join_dim,)),
             ("joint.ffn_out.weight", (c.vocab, c.join_dim)), ("joint.ffn_out.bias", (c.vocab,))]
     return out
@@ -95,6 +154,10 @@ def synthetic_transducer_state_dict(c: RNNTConfig, seed: int = 0, blank_bias: fl
         elif name.startswith("predictor.rnn."):
             a = 1.0 / math.sqrt(c.hidden)
             t = (torch.rand(shape, generator=g) * 2 - 1) * a
+        elif name.startswith("predictor.norm."):
+            t = torch.ones(shape) if name.endswith("weight") else torch.zeros(shape)
+        elif name.startswith("predictor.conv."):   # Conv1d, groups = channels: fan_in = kernel size
+            t = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(c.context)
         else:
             fan = shapes[name[: -len("bias")] + "weight"][1] if name.endswith("bias") else shape[1]
             t = (torch.rand(shape, generator=g) * 2 - 1) / math.sqrt(fan)
@@ -199,6 +262,10 @@ class RNNTGreedy:
                 raise ValueError(f"weight {name}: shape {tuple(state_dict[name].shape)} != {shape}")
         c = _lib.CfmRnntConfig(cfg.vocab, cfg.enc_dim, cfg.embed_size, cfg.hidden, cfg.num_layers, cfg.pred_out,
                                cfg.join_dim, cfg.blank)
+        pc = None
+        if cfg.stateless:
+            pc = _lib.CfmRnntPredictorConfig(PREDICTORS.index(cfg.predictor), cfg.history_size, cfg.n_head,
+                                             PREDICTOR_ACTS.index(cfg.act), int(cfg.conv_bias), cfg.ln_eps)
         names = [n for n, _ in schema(cfg)]
         keep = []
         views = (_lib.CfmTensorView * len(names))()
@@ -208,8 +275,12 @@ class RNNTGreedy:
             views[i] = _lib.CfmTensorView(k.encode(), t.data_ptr(), t.numel())
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.cfm_rnnt_create(ctypes.byref(c), views, len(names), self.device.index or 0,
-                                            ctypes.byref(h)))
+            if pc is None:
+                _lib.check(_lib.cfm_rnnt_create(ctypes.byref(c), views, len(names), self.device.index or 0,
+                                                ctypes.byref(h)))
+            else:
+                _lib.check(_lib.cfm_rnnt_create_ex(ctypes.byref(c), ctypes.byref(pc), views, len(names),
+                                                   self.device.index or 0, ctypes.byref(h)))
         self._h = h
         self.grid_fallbacks = 0   # searches the multi-CU kernel left early (barrier timeout), rerun on one workgroup
         self._finalizer = weakref.finalize(self, _lib.cfm_rnnt_destroy, ctypes.c_void_p(h.value))

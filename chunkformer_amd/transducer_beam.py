@@ -87,17 +87,82 @@ def beam_step_host(hyps: Sequence[Tuple[int, ...]], scores: Sequence[float], top
 
 
 # ----------------------------------------------------------------------------- predictor and joint on the host
+_ACTS = {"relu": torch.relu, "swish": torch.nn.functional.silu, "tanh": torch.tanh, "gelu": torch.nn.functional.gelu}
+
+
+def hyp_windows(cfg: RNNTConfig, hyp: Sequence[int]) -> np.ndarray:
+    """The id windows [U + 1, history_size + 1] of the states of [blank, y_1 .. y_U] (oldest id first, -1 = a position
+    before the sos: a zero vector)."""
+    seq = [-1] * cfg.history_size + [cfg.blank] + [int(t) for t in hyp]
+    K = cfg.context
+    return np.array([seq[u: u + K] for u in range(len(hyp) + 1)], dtype=np.int64).reshape(len(hyp) + 1, K)
+
+
 class HostTransducer:
-    """The reference's RNNPredictor (lstm) + TransducerJoint math in torch f32 on the CPU, from a state dict."""
+    """The reference's predictor (RNNPredictor lstm, EmbeddingPredictor or ConvPredictor) + TransducerJoint math in
+    torch f32 on the CPU, from a state dict."""
 
     def __init__(self, cfg: RNNTConfig, state_dict: Dict[str, torch.Tensor]):
         self.cfg = cfg
         sd = {k: v.detach().to("cpu", torch.float32) for k, v in state_dict.items()
               if k.startswith(("predictor.", "joint."))}
         self.sd = sd
+        if cfg.stateless:
+            return
         self.rnn = torch.nn.LSTM(cfg.embed_size, cfg.hidden, cfg.num_layers, bias=True, batch_first=True)
         self.rnn.load_state_dict({k[len("predictor.rnn."):]: v for k, v in sd.items() if k.startswith("predictor.rnn.")})
         self.rnn.eval()
+
+    # ---- the stateless predictors: the state of a hypothesis is its id window
+    def _context_rows(self, windows, dtype) -> torch.Tensor:
+        """[n, K] ids (-1 = before the sos) -> their embedding rows [n, K, E] in `dtype`, zero vectors for -1."""
+        w = torch.as_tensor(np.asarray(windows), dtype=torch.long).reshape(-1, self.cfg.context)
+        rows = self.sd["predictor.embed.weight"].to(dtype)[w.clamp(min=0)]
+        return rows * (w >= 0).unsqueeze(-1).to(dtype)
+
+    def _norm_act(self, x: torch.Tensor, dtype) -> torch.Tensor:
+        cfg = self.cfg
+        y = torch.nn.functional.layer_norm(x, (cfg.embed_size,), self.sd["predictor.norm.weight"].to(dtype),
+                                           self.sd["predictor.norm.bias"].to(dtype), cfg.ln_eps)
+        return _ACTS[cfg.act](y)
+
+    @torch.no_grad()
+    def predict_windows(self, windows, dtype=torch.float64) -> torch.Tensor:
+        """The predictor as a pure context function: windows [n, K] -> outputs [n, E] in `dtype`.
+        embedding: x = sum_c (c_c . q_c) c_c / (n_head K), q_c the heads of pos_embed summed; y = act(LN(ffn(x))).
+        conv: x[d] = sum_c w[d, 0, c] c_c[d] (+ bias); y = act(LN(x))."""
+        cfg = self.cfg
+        E, K = cfg.embed_size, cfg.context
+        c = self._context_rows(windows, dtype)                                               # [n, K, E]
+        if cfg.predictor == "embedding":
+            q = self.sd["predictor.pos_embed.weight"].to(dtype).view(cfg.n_head, E, K).sum(0).t()   # [K, E]
+            x = ((c * q).sum(-1, keepdim=True) * c).sum(1) / (cfg.n_head * K)
+            x = torch.nn.functional.linear(x, self.sd["predictor.ffn.weight"].to(dtype),
+                                           self.sd["predictor.ffn.bias"].to(dtype))
+        else:
+            x = (c * self.sd["predictor.conv.weight"].to(dtype)[:, 0, :].t()).sum(1)
+            if cfg.conv_bias:
+                x = x + self.sd["predictor.conv.bias"].to(dtype)
+        return self._norm_act(x, dtype)
+
+    @torch.no_grad()
+    def step_windows(self, windows) -> torch.Tensor:
+        """forward_step in f32 with the reference's tensor shapes (predictor.py:322-362, 450-471): windows [n, K] ->
+        the predictor outputs [n, 1, E]."""
+        cfg = self.cfg
+        E, K = cfg.embed_size, cfg.context
+        ctx = self._context_rows(windows, torch.float32)                                     # [n, K, E]
+        if cfg.predictor == "embedding":
+            ex = ctx.unsqueeze(1).unsqueeze(2)                                               # [n, 1, 1, K, E]
+            pos = self.sd["predictor.pos_embed.weight"].view(cfg.n_head, E, K).permute(0, 2, 1)
+            wgt = (ex * pos).sum(dim=-1).unsqueeze(3)                                        # [n, 1, heads, 1, K]
+            out = wgt.matmul(ex).squeeze(dim=3).sum(dim=2) / (cfg.n_head * K)                # [n, 1, E]
+            out = torch.nn.functional.linear(out, self.sd["predictor.ffn.weight"], self.sd["predictor.ffn.bias"])
+        else:
+            out = torch.nn.functional.conv1d(ctx.permute(0, 2, 1), self.sd["predictor.conv.weight"],
+                                             self.sd.get("predictor.conv.bias") if cfg.conv_bias else None,
+                                             groups=E).permute(0, 2, 1)
+        return self._norm_act(out, torch.float32)
 
     @torch.no_grad()
     def step(self, tokens: Sequence[int], h: torch.Tensor, c: torch.Tensor):
@@ -130,15 +195,23 @@ def _search_one_host(m: HostTransducer, enc: torch.Tensor, ctc: Optional[torch.T
     T = enc.shape[0]
     hyps: List[Tuple[int, ...]] = [()]
     scores, times = [0.0], [()]
-    h = torch.zeros(cfg.num_layers, 1, cfg.hidden)
-    c = torch.zeros(cfg.num_layers, 1, cfg.hidden)
+    sl = cfg.stateless
+    if sl:
+        hist = [(-1,) * cfg.history_size]   # per hypothesis the ids before its last token
+    else:
+        h = torch.zeros(cfg.num_layers, 1, cfg.hidden)
+        c = torch.zeros(cfg.num_layers, 1, cfg.hidden)
     tr = {"parent": np.full((T, K), -1, np.int32), "token": np.full((T, K), -1, np.int32),
           "score": np.zeros((T, K), np.float64), "topv": np.zeros((T, K, K), np.float32),
           "topi": np.full((T, K, K), -1, np.int32), "n": np.zeros(T, np.int32)}
     margin, fusions = math.inf, 0
     for t in range(T):
         last = [hyp[-1] if hyp else cfg.blank for hyp in hyps]
-        pred, hn, cn = m.step(last, h, c)
+        if sl:
+            wins = [hs + (tk,) for hs, tk in zip(hist, last)]
+            pred = m.step_windows(wins)
+        else:
+            pred, hn, cn = m.step(last, h, c)
         fused = fuse_host(m.log_probs(enc[t], pred), ctc[t] if ctc is not None else None, cw, tw).numpy()
         topv, topi = topk_rows_host(fused, K)
         n = len(hyps)
@@ -156,10 +229,13 @@ def _search_one_host(m: HostTransducer, enc: torch.Tensor, ctc: Optional[torch.T
         tr["topv"][t, :n], tr["topi"][t, :n], tr["n"][t] = topv, topi, len(kept)
         for r, (hyp, s, par, u, app) in enumerate(kept):
             tr["parent"][t, r], tr["token"][t, r], tr["score"][t, r] = par, u, s
-        par = torch.as_tensor([k[2] for k in kept], dtype=torch.long)
-        app = torch.as_tensor([k[4] for k in kept]).view(1, -1, 1)
-        h = torch.where(app, hn[:, par], h[:, par])
-        c = torch.where(app, cn[:, par], c[:, par])
+        if sl:   # a token extension shifts the window by the parent's last token, a blank keeps it
+            hist = [wins[k[2]][1:] if k[4] else hist[k[2]] for k in kept]
+        else:
+            par = torch.as_tensor([k[2] for k in kept], dtype=torch.long)
+            app = torch.as_tensor([k[4] for k in kept]).view(1, -1, 1)
+            h = torch.where(app, hn[:, par], h[:, par])
+            c = torch.where(app, cn[:, par], c[:, par])
         times = [times[k[2]] + (t,) if k[4] else times[k[2]] for k in kept]
         hyps, scores = [k[0] for k in kept], [k[1] for k in kept]
     res = DecodeResult(list(hyps[0]), scores[0], times=list(times[0]), nbest=[list(x) for x in hyps],
@@ -189,6 +265,48 @@ def prefix_beam_search_host(model, enc_rows: torch.Tensor, ctc_logp: Optional[to
     del return_trace   # the host search always records it
     return [_search_one_host(m, enc[s: s + n], ctc[s: s + n] if use_ctc else None, int(beam_size), ctc_weight,
                              transducer_weight) for s, n in zip(rs, rl)]
+
+
+@torch.no_grad()
+def greedy_host(model, enc_rows: torch.Tensor, row_start, row_len, n_steps: int = 64):
+    """basic_greedy_search (transducer/search/greedy_search.py) per utterance of a packed batch over a HostTransducer (or
+    a (RNNTConfig, state_dict) pair), any predictor kind: the predictor is re-evaluated only after a non-blank decision
+    and a frame ends on blank or after n_steps non-blanks.  Returns (dense [rows, n_steps] int32 as
+    RNNTGreedy.greedy_packed, the smallest top-1 - top-2 logit gap over all decisions)."""
+    m = model if isinstance(model, HostTransducer) else HostTransducer(*model)
+    cfg = m.cfg
+    enc = torch.as_tensor(enc_rows, dtype=torch.float32).reshape(-1, cfg.enc_dim).cpu()
+    from . import _lib
+    rs, rl = (t.tolist() for t in _lib.packed_ranges(row_start, row_len, enc.shape[0], "encoder rows"))
+    lin = torch.nn.functional.linear
+    dense = np.zeros((enc.shape[0], int(n_steps)), np.int32)
+    gap = math.inf
+    for s, n in zip(rs, rl):
+        if cfg.stateless:
+            win = (-1,) * cfg.history_size + (cfg.blank,)
+            pred = m.step_windows([win])
+        else:
+            h = torch.zeros(cfg.num_layers, 1, cfg.hidden)
+            c = torch.zeros(cfg.num_layers, 1, cfg.hidden)
+            pred, hn, cn = m.step([cfg.blank], h, c)
+        for t in range(n):
+            e = lin(enc[s + t].reshape(1, 1, -1), m.sd["joint.enc_ffn.weight"], m.sd["joint.enc_ffn.bias"])
+            for step in range(int(n_steps)):
+                p = lin(pred, m.sd["joint.pred_ffn.weight"], m.sd["joint.pred_ffn.bias"])
+                logits = lin(torch.tanh(e + p), m.sd["joint.ffn_out.weight"], m.sd["joint.ffn_out.bias"]).reshape(-1)
+                top = torch.topk(logits, 2).values
+                gap = min(gap, float(top[0] - top[1]))
+                k = int(torch.argmax(logits))
+                if k == cfg.blank:
+                    break
+                dense[s + t, step] = k
+                if cfg.stateless:
+                    win = win[1:] + (k,)
+                    pred = m.step_windows([win])
+                else:
+                    h, c = hn, cn
+                    pred, hn, cn = m.step([k], h, c)
+    return dense, gap
 
 
 # ----------------------------------------------------------------------------- the device search
@@ -281,6 +399,25 @@ class RNNTBeamSearch:
                                                   torch.cuda.current_stream(dev).cuda_stream))
             torch.cuda.current_stream(dev).synchronize()
         return ho, co, pj
+
+    @torch.no_grad()
+    def predictor_step(self, tokens_ctx):
+        """cfm_op_rnnt_predictor_step (a stateless handle): id windows [R, history_size + 1] (oldest first, -1 = before
+        the sos) -> (predictor output [R, embed_size], its pred_ffn projection [R, join_dim]) on the device."""
+        from . import _lib
+        cfg, dev = self.cfg, self.device
+        win = tokens_ctx if isinstance(tokens_ctx, torch.Tensor) else torch.as_tensor(np.asarray(tokens_ctx))
+        win = win.reshape(-1, cfg.context).to(dev, torch.int32).contiguous()
+        R = int(win.shape[0])
+        y = torch.empty(R, cfg.embed_size, dtype=torch.float32, device=dev)
+        pj = torch.empty(R, cfg.join_dim, dtype=torch.float32, device=dev)
+        nbytes = int(_lib.cfm_op_rnnt_predictor_step_workspace_bytes(self.rnnt._h, R))
+        ws = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.cfm_op_rnnt_predictor_step(self.rnnt._h, win.data_ptr(), R, y.data_ptr(), pj.data_ptr(),
+                                                       ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream))
+            torch.cuda.current_stream(dev).synchronize()
+        return y, pj
 
 
 @torch.no_grad()

@@ -63,9 +63,13 @@ def joint_projections_host(host_transducer, enc, hyp: Sequence[int], dtype=torch
     W = {k: v.to(dtype) for k, v in m.sd.items()}
     lin = torch.nn.functional.linear
     x = torch.as_tensor(enc).reshape(-1, cfg.enc_dim).to(dtype)
-    emb = W["predictor.embed.weight"][torch.tensor([cfg.blank] + [int(t) for t in hyp], dtype=torch.long)].unsqueeze(0)
-    out, _ = _host_rnn(m, dtype)(emb)
-    p = lin(out[0], W["predictor.projection.weight"], W["predictor.projection.bias"])            # [U + 1, P]
+    if cfg.stateless:   # state u = the context function of the last history_size + 1 ids of [blank, y_1 .. y_u]
+        from .transducer_beam import hyp_windows
+        p = m.predict_windows(hyp_windows(cfg, hyp), dtype)                                      # [U + 1, E]
+    else:
+        emb = W["predictor.embed.weight"][torch.tensor([cfg.blank] + [int(t) for t in hyp], dtype=torch.long)].unsqueeze(0)
+        out, _ = _host_rnn(m, dtype)(emb)
+        p = lin(out[0], W["predictor.projection.weight"], W["predictor.projection.bias"])        # [U + 1, P]
     e = lin(x, W["joint.enc_ffn.weight"], W["joint.enc_ffn.bias"])                               # [T, J]
     q = lin(p, W["joint.pred_ffn.weight"], W["joint.pred_ffn.bias"])                             # [U + 1, J]
     return e, q

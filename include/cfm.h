@@ -356,6 +356,38 @@ typedef struct cfm_rnnt cfm_rnnt;
  * predictor.projection.{weight,bias}, joint.{enc_ffn,pred_ffn,ffn_out}.{weight,bias} */
 cfm_status cfm_rnnt_create(const cfm_rnnt_config* cfg, const cfm_tensor_view* weights, int32_t n_weights,
                            int32_t device, cfm_rnnt** out);
+/* The reference's two stateless predictors (transducer/predictor.py:210-471) over the same joint: the output is a
+ * function of the last history_size + 1 tokens, positions before the sos being zero vectors (init_state), not the
+ * blank's embedding.
+ *   CFM_RNNT_PRED_EMBEDDING (arXiv 2109.07513): x = sum_c (c_c . q_c) c_c / (n_head * K), q_c[d] = sum over heads of
+ *     pos_embed.weight[head, d * K + c]; y = act(LayerNorm(ffn(x))).  Keys: predictor.embed.weight,
+ *     predictor.pos_embed.weight [n_head, E * K] (pos_embed.bias is accepted and, as in the reference, never read),
+ *     predictor.ffn.{weight,bias}, predictor.norm.{weight,bias}.
+ *   CFM_RNNT_PRED_CONV: x[d] = sum_c conv.weight[d, 0, c] c_c[d] (+ conv.bias[d] with conv_bias); y = act(LayerNorm(x)).
+ *     Keys: predictor.embed.weight, predictor.conv.weight [E, 1, K], predictor.conv.bias (conv_bias only),
+ *     predictor.norm.{weight,bias}.
+ * Both feed joint.pred_ffn as a separate [join_dim, E] product.  For these kinds cfg->hidden and cfg->num_layers are
+ * ignored and cfg->embed_size == cfg->pred_out is required (CFM_ERR_ASSERT otherwise).  kind CFM_RNNT_PRED_RNN with a
+ * null or any pcfg is cfm_rnnt_create.  Every other cfm_rnnt_* entry point works on either kind of handle.  The
+ * multi-CU greedy search is not built for a stateless handle: cfm_rnnt_grid_blocks returns 0 and the option
+ * "grid_blocks" is accepted and has no effect. */
+#define CFM_RNNT_PRED_RNN 0
+#define CFM_RNNT_PRED_EMBEDDING 1
+#define CFM_RNNT_PRED_CONV 2
+#define CFM_RNNT_ACT_RELU 0
+#define CFM_RNNT_ACT_SWISH 1
+#define CFM_RNNT_ACT_TANH 2
+#define CFM_RNNT_ACT_GELU 3
+typedef struct {
+  int32_t kind;          /* CFM_RNNT_PRED_* */
+  int32_t history_size;  /* 0 .. 8 */
+  int32_t n_head;        /* embedding: >= 1 */
+  int32_t activation;    /* CFM_RNNT_ACT_* */
+  int32_t conv_bias;     /* conv: predictor.conv.bias is present and added */
+  float ln_eps;          /* layer_norm_epsilon */
+} cfm_rnnt_predictor_config;
+cfm_status cfm_rnnt_create_ex(const cfm_rnnt_config* cfg, const cfm_rnnt_predictor_config* pcfg,
+                              const cfm_tensor_view* weights, int32_t n_weights, int32_t device, cfm_rnnt** out);
 void cfm_rnnt_destroy(cfm_rnnt* h);
 size_t cfm_rnnt_workspace_bytes(const cfm_rnnt* h, int32_t rows);
 /* Greedy search of utterances b = rows [row_start[b], row_start[b] + row_len[b]) of enc_dev
@@ -393,7 +425,9 @@ int32_t cfm_rnnt_error(const cfm_rnnt* h, const void* workspace, int32_t rows);
  *   enc_dev [rows, enc_dim] f32; ctc_logp_dev [rows, vocab] f32 (what cfm_ctc_logprobs writes) or null with
  *   ctc_weight == 0; utterance b = rows [row_start[b], + row_len[b]) (device int32 [B]); max_len >= every row_len
  *   (the host's frame count); beam 1 .. 16 and <= vocab; weights >= 0, not both 0.  embed_size, hidden_size and
- *   join_dim must be multiples of 32 (CFM_ERR_ASSERT otherwise).
+ *   join_dim must be multiples of 32 (CFM_ERR_ASSERT otherwise).  A stateless handle (cfm_rnnt_create_ex) runs its
+ *   context kernel, LayerNorm + activation and f32 GEMMs per frame in place of the LSTM steps, and a slot's state is
+ *   history_size int32 ids: its workspace is the smaller for it.
  * Outputs, for up to `beam` hypotheses per utterance in final (score-descending) order:
  *   out_tokens / out_times [beam, rows] int32: hypothesis k of utterance b at [k * rows + row_start[b] ..), the frame
  *   at which each token was appended beside it; out_len [B, beam]; out_score [B, beam] f64; n_hyps [B].
@@ -421,7 +455,9 @@ int32_t cfm_rnnt_beam_error(const void* workspace);
  *   tokens_dev [n_states] int32: state u of hypothesis i at first_state + u holds the token the predictor consumed to
  *     reach it (the blank for u = 0, y_u after); desc_dev [n_hyp][4] int32 = (utt, first_state, U + 1, 0);
  *   node0_dev [n_hyp + 1] int64: the running sum of T * (U + 1), node0[n_hyp] = total_nodes; max_u1 >= every U + 1.
- * One call = enc_ffn over the rows, max_u1 predictor steps over all hypotheses, the joint lattice kernel (per node
+ * One call = enc_ffn over the rows, max_u1 predictor steps over all hypotheses (a stateless handle: one predictor
+ * pass over all n_states states, state s of a hypothesis reading tokens[max(first_state, s - history_size) .. s] and
+ * zero vectors before first_state), the joint lattice kernel (per node
  * only b = log p(blank) and k = log p(next token), f32; `dtype` selects exact f32 MFMA operands (CFM_DTYPE_F32) or
  * bf16 operands with f32 accumulation (CFM_DTYPE_BF16), -1 the handle's "lattice_dtype" option, so that callers of
  * different types share a handle without touching its state) and the f64 recursion

@@ -200,6 +200,13 @@ size_t cfm_op_rnnt_lstm_step_workspace_bytes(const cfm_rnnt* h, int32_t R);
 cfm_status cfm_op_rnnt_lstm_step(cfm_rnnt* h, const int32_t* tokens, const float* h_in, const float* c_in, int32_t R,
                                  float* h_out, float* c_out, float* pred_out, void* workspace, size_t workspace_bytes,
                                  cfm_stream stream);
+/* predictor_step (a stateless handle only: CFM_ERR_VALUE on an LSTM one): the context kernel, the ffn GEMM (embedding),
+ * LayerNorm + activation and the pred_ffn GEMM for R id windows: windows [R, history_size + 1] int32, oldest id
+ * first, -1 = a position before the sos (a zero vector) -> y_out [R, embed_size] (the predictor output) and
+ * pred_out [R, join_dim] (its pred_ffn projection). */
+size_t cfm_op_rnnt_predictor_step_workspace_bytes(const cfm_rnnt* h, int32_t R);
+cfm_status cfm_op_rnnt_predictor_step(cfm_rnnt* h, const int32_t* windows, int32_t R, float* y_out, float* pred_out,
+                                      void* workspace, size_t workspace_bytes, cfm_stream stream);
 
 /* The kernels of the full-sum transducer score (csrc/rnnt_lattice.hip, cfm_rnnt_td_score in cfm.h), one at a time.
  * lattice: the joint over the lattice nodes of cfm_rnnt_td_score's descriptors from given projections: enc_proj

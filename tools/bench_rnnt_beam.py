@@ -1,7 +1,8 @@
 """Measure the transducer prefix beam search (decoding_method "rnnt_beam_search"): the device search against the
 reference's formulation in torch.
 
-    python tools/bench_rnnt_beam.py [--iters 3] [--cases a,b,c] [--beams 5,10] [--baseline-frames 200] [--out profiles/NAME.json]
+    python tools/bench_rnnt_beam.py [--iters 3] [--cases a,b,c] [--beams 5,10] [--baseline-frames 200]
+                                    [--predictor rnn|embedding|conv] [--out profiles/NAME.json]
 
 Model: the vie recipe's predictor and joint (embed 256, LSTM 2 x 512, join_dim 512) at enc_dim 512, V = 1,024, seeded
 weights with blank_bias 7 (transducer.synthetic_transducer_state_dict); random encoder rows, CTC log-probs from seeded
@@ -27,6 +28,13 @@ Split of our frame, from calls of their own on the search's shapes (include/cfm_
 host_bound: the wall time the host needs to enqueue the whole search (no synchronisation) over the device time of the
 same search.  Near 1 either the host is the bound or the enqueueing call ran into the queue's depth and waited for
 the device (searches of thousands of frames); the short case (b) shows the enqueue cost alone.
+
+`--predictor embedding|conv` measures a stateless handle of equal widths (embed = output = 512, history 2, 4 heads)
+instead, beside the LSTM handle in the same process on the same inputs (boxes differ by 1-3%): per case and beam the
+whole search and the predictor pass alone (cfm_op_rnnt_predictor_step / cfm_op_rnnt_lstm_step for B x beam rows) of
+both handles, and the greedy search at B = 1 (2,000 rows, n_steps 4, blank_bias 3.72: most frames emit) in ms per
+emission -- the stateless one-workgroup kernel beside the LSTM's one-workgroup and multi-CU kernels.  The torch
+baseline is not run in this form.
 
 Prints one JSON line; --out also writes it to a file.
 """
@@ -190,12 +198,69 @@ def run_case(TB, _lib, search, W, rnn, cfg, B, T, K, seed, iters, base_frames):
             "workspace_bytes": nbytes}
 
 
+def stateless_compare(TB, _lib, kind, cases, beams, iters):
+    from chunkformer_amd.transducer import RNNTConfig, RNNTGreedy, synthetic_transducer_state_dict
+    scfg = RNNTConfig(vocab=1024, embed_size=512, hidden=0, num_layers=0, pred_out=512, join_dim=512, predictor=kind,
+                      history_size=2, n_head=4)
+    lcfg = RNNTConfig(vocab=1024)
+    res = {"predictor": kind, "stateless_model": {k: getattr(scfg, k) for k in ("embed_size", "join_dim", "history_size", "n_head")}}
+    handles = {}
+    for key, cfg in (("stateless", scfg), ("lstm", lcfg)):
+        handles[key] = {bb: TB.RNNTBeamSearch(RNNTGreedy(cfg, synthetic_transducer_state_dict(cfg, 0, blank_bias=bb), "cuda"))
+                        for bb in (7.0, 3.72)}
+    dev = handles["lstm"][7.0].device
+    for name, B, T, seed in cases:
+        rng = np.random.default_rng(seed)
+        rows, starts = [T] * B, [b * T for b in range(B)]
+        enc = torch.from_numpy(rng.standard_normal((B * T, lcfg.enc_dim)).astype(np.float32)).to(dev)
+        g = torch.Generator().manual_seed(seed)
+        ctc = (torch.randn(B * T, lcfg.vocab, generator=g) * 2.0).to(dev).log_softmax(-1)
+        for K in beams:
+            out = {"utterances": B, "rows_per_utterance": T, "beam": K}
+            R = B * K
+            for key in ("stateless", "lstm"):
+                s = handles[key][7.0]
+                s.search_packed(enc, ctc, starts, rows, K, 0.3, 0.7)
+                torch.cuda.synchronize()
+                ts = [timed(lambda: s.search_packed(enc, ctc, starts, rows, K, 0.3, 0.7)) for _ in range(iters)]
+                if key == "stateless":
+                    win = torch.randint(0, 1024, (R, scfg.context), generator=g).to(dev, torch.int32)
+                    s.predictor_step(win)
+                    tp = statistics.median([timed(lambda: s.predictor_step(win)) for _ in range(5)])
+                else:
+                    tok = torch.zeros(R, dtype=torch.int32, device=dev)
+                    h0 = torch.zeros(lcfg.num_layers, R, lcfg.hidden, device=dev)
+                    s.lstm_step(tok, h0, h0)
+                    tp = statistics.median([timed(lambda: s.lstm_step(tok, h0, h0)) for _ in range(5)])
+                out[key] = dict(spread(ts), ms_per_frame=statistics.median(ts) / T, predictor_op_ms=tp,
+                                workspace_bytes=int(_lib.cfm_rnnt_beam_workspace_bytes(s.rnnt._h, B * T, B, K)))
+            out["stateless_over_lstm"] = out["stateless"]["median_ms"] / out["lstm"]["median_ms"]
+            res[f"{name}_beam{K}"] = out
+    # greedy at B = 1
+    T = 2000
+    enc = torch.from_numpy(np.random.default_rng(5).standard_normal((T, lcfg.enc_dim)).astype(np.float32)).to(dev)
+    gr = {}
+    for key, grid in (("stateless", None), ("lstm_one_workgroup", 0), ("lstm_multi_cu", 32)):
+        r = handles["stateless" if key == "stateless" else "lstm"][3.72].rnnt
+        if grid is not None:
+            r.set_option("grid_blocks", grid)
+        dense = r.greedy_packed(enc, [0], [T], 4)
+        torch.cuda.synchronize()
+        ts = [timed(lambda: r.greedy_packed(enc, [0], [T], 4)) for _ in range(iters)]
+        em = int((dense != 0).sum())
+        gr[key] = dict(spread(ts), rows=T, emissions=em, ms_per_emission=statistics.median(ts) / max(em, 1),
+                       grid_blocks=r.grid_blocks(1))
+    res["greedy_b1"] = gr
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--cases", default="a,b,c")
     ap.add_argument("--beams", default="5,10")
     ap.add_argument("--baseline-frames", type=int, default=200)
+    ap.add_argument("--predictor", default="rnn", choices=("rnn", "embedding", "conv"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -203,6 +268,18 @@ def main():
     from chunkformer_amd import _lib
     from chunkformer_amd import transducer_beam as TB
     from chunkformer_amd.transducer import RNNTConfig, RNNTGreedy, synthetic_transducer_state_dict
+    shapes = {"a": ("batch_240min", 70, 2601), "b": ("batch_256_short", 256, 374), "c": ("endless_one_utterance", 1, 45000)}
+    if a.predictor != "rnn":
+        res = stateless_compare(TB, _lib, a.predictor, [shapes[k] + (1 + ord(k),) for k in a.cases.split(",")],
+                                [int(v) for v in a.beams.split(",")], a.iters)
+        res["device"] = torch.cuda.get_device_name(0)
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     cfg = RNNTConfig(vocab=1024)
     sd = synthetic_transducer_state_dict(cfg, 0, blank_bias=7.0)
     search = TB.RNNTBeamSearch(RNNTGreedy(cfg, sd, "cuda"))
@@ -213,7 +290,6 @@ def main():
     rnn.eval()
     res = {"device": torch.cuda.get_device_name(0), "dtype": "f32", "iters": a.iters, "weights": [0.3, 0.7],
            "model": {k: getattr(cfg, k) for k in ("vocab", "enc_dim", "embed_size", "hidden", "num_layers", "join_dim")}}
-    shapes = {"a": ("batch_240min", 70, 2601), "b": ("batch_256_short", 256, 374), "c": ("endless_one_utterance", 1, 45000)}
     for key in a.cases.split(","):
         name, B, T = shapes[key]
         for K in (int(v) for v in a.beams.split(",")):

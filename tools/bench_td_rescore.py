@@ -2,7 +2,8 @@
 / "ctc_beam_td_attn_rescoring"): cfm_rnnt_td_score and its two kernels, fp32 and bf16, against the reference's
 formulation in torch.
 
-    python tools/bench_td_rescore.py [--iters 3] [--cases a,b] [--utts-a N] [--utts-b N] [--out profiles/NAME.json]
+    python tools/bench_td_rescore.py [--iters 3] [--cases a,b] [--utts-a N] [--utts-b N] [--predictor rnn|embedding|conv]
+                                     [--out profiles/NAME.json]
 
 Model: the vie recipe's predictor and joint (embed 256, LSTM 2 x 512, join_dim J = 512) at enc_dim 512, V = 1,024,
 seeded weights (transducer.synthetic_transducer_state_dict); random encoder rows; 10 random hypotheses per utterance.
@@ -23,6 +24,11 @@ logits, log_softmax, and the gather of the blank and target log-probs.  It cover
 input of rnnt_loss and, instead of torchaudio's loss kernel (not installed here), nothing: the recursion is left out
 of the baseline, so the comparison favours the baseline.  It is timed for `--baseline-utts` utterances and scaled to
 the case (one utterance at a time, as the reference's batch size 1 has it).
+
+`--predictor embedding|conv` adds, per case, the predictor's share of a td call for a stateless handle of equal widths
+(embed = output = 512, history 2, 4 heads) beside the LSTM handle in the same process on the same inputs (fp32): the
+whole call of each, and the predictor pass alone -- one cfm_op_rnnt_predictor_step over all the group's states for the
+stateless handle, max(U + 1) cfm_op_rnnt_lstm_step calls over the group's hypotheses for the LSTM (as the call runs them).
 
 Prints one JSON line; --out also writes it to a file.
 """
@@ -75,6 +81,50 @@ def baseline_one(sd, cfg, rnn, enc, hyps):
     return lp[..., cfg.blank], lp.gather(-1, tgt.view(n, 1, U + 1, 1).expand(n, enc.shape[0], U + 1, 1))
 
 
+def stateless_config(kind):
+    from chunkformer_amd.transducer import RNNTConfig
+    return RNNTConfig(embed_size=512, hidden=0, num_layers=0, pred_out=512, join_dim=512, predictor=kind, history_size=2,
+                      n_head=4)
+
+
+def predictor_share(kind, rnnt, enc, starts, lens, nbest, iters):
+    """The predictor pass alone and the whole fp32 td call, stateless handle and LSTM handle, same inputs."""
+    from chunkformer_amd.transducer import RNNTGreedy, synthetic_transducer_state_dict
+    from chunkformer_amd.transducer_beam import RNNTBeamSearch, hyp_windows
+    from chunkformer_amd.transducer_rescore import TransducerRescorer, _groups
+    dev = enc.device
+    scfg = stateless_config(kind)
+    sl = RNNTGreedy(scfg, synthetic_transducer_state_dict(scfg, 3, blank_bias=7.0), dev)
+    out = {"kind": kind}
+    T = lens[0]
+    nodes = [T * (len(h) + 1) for hyps in nbest for h in hyps]
+    flat = [h for hyps in nbest for h in hyps]
+    for key, handle in (("stateless", sl), ("lstm", rnnt)):
+        tr = TransducerRescorer(handle, None, "fp32")
+        tr.td_scores(enc, starts, lens, nbest)
+        whole = statistics.median([timed(lambda: tr.td_scores(enc, starts, lens, nbest)) for _ in range(iters)])
+        groups = _groups(nodes, tr.max_lattice_bytes)
+        bs = RNNTBeamSearch(handle)
+        pred = 0.0
+        for grp in groups:
+            hyps = [flat[j] for j in grp]
+            if key == "stateless":
+                win = torch.from_numpy(np.concatenate([hyp_windows(scfg, h) for h in hyps])).to(dev, torch.int32)
+                bs.predictor_step(win)
+                pred += statistics.median([timed(lambda: bs.predictor_step(win)) for _ in range(iters)])
+            else:
+                c = handle.cfg
+                n, steps = len(hyps), max(len(h) for h in hyps) + 1
+                tok = torch.zeros(n, dtype=torch.int32, device=dev)
+                h0 = torch.zeros(c.num_layers, n, c.hidden, device=dev)
+                bs.lstm_step(tok, h0, h0)
+                pred += statistics.median([timed(lambda: bs.lstm_step(tok, h0, h0)) for _ in range(iters)]) * steps
+        out[key] = {"whole_ms": whole, "predictor_alone_ms": pred, "predictor_share": pred / whole,
+                    "device_calls": len(groups)}
+    out["stateless_over_lstm_whole"] = out["stateless"]["whole_ms"] / out["lstm"]["whole_ms"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=3)
@@ -82,6 +132,7 @@ def main():
     ap.add_argument("--utts-a", type=int, default=256)
     ap.add_argument("--utts-b", type=int, default=70)
     ap.add_argument("--baseline-utts", type=int, default=4)
+    ap.add_argument("--predictor", default="rnn", choices=("rnn", "embedding", "conv"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     from chunkformer_amd.transducer import RNNTConfig, RNNTGreedy, synthetic_transducer_state_dict
@@ -140,6 +191,8 @@ def main():
                                              covers="predictor, joint tensor, log_softmax, gather; not the loss recursion")
             for dtype in ("fp32", "bf16"):
                 out[dtype]["speedup_vs_baseline"] = out["baseline_torch_f32"]["scaled_to_case_ms"] / out[dtype]["whole"]["median_ms"]
+        if args.predictor != "rnn":
+            out["predictor"] = predictor_share(args.predictor, rnnt, enc, starts, lens, nbest, args.iters)
         res["cases"][name] = out
     line = json.dumps(res)
     print(line)
